@@ -522,7 +522,31 @@ def spawn_ranks(n, argv):
     return subprocess.call(cmd, env=env)
 
 
-def measure(args, cfg_name, sizes, comm, rank, world, local_rank, on_gpu, custom=False):
+DUMP_MAX_BYTES = (64 << 20) - (1 << 16)        # 64 MB in all, less room for the .npy headers
+
+
+def dump_outputs(path, res, M):
+    """What the timed path hands its caller after the last timed step, as DIR/<name>.npy in float64: Master.run's moments
+    of that step (m_phi, cov_phi) and its msteps / mrhats (not the wall times), the global natural parameters (Q, r) and
+    this rank's site parameters (Qi, ri).  Site parameters beyond the size cap are a fixed sample of sites (seeded, the
+    same for the same arguments), listed in site_index."""
+    (m_s, S_s), (_, msteps, mrhats, _) = res[1], res[2]
+    out = {'m_phi': m_s[-1], 'cov_phi': S_s[-1], 'msteps': msteps[-1:], 'mrhats': mrhats[-1:], 'Q': M.Q, 'r': M.r}
+    lo, hi = M.k_lo, M.k_hi
+    per_site = (M.dphi ** 2 + M.dphi) * 8
+    room = (DUMP_MAX_BYTES - sum(np.asarray(a).size * 8 for a in out.values())) // (per_site + 8)
+    idx = np.arange(hi - lo)
+    if len(idx) > room:
+        idx = np.sort(np.random.RandomState(0).choice(len(idx), int(room), replace=False))
+    out['site_index'] = lo + idx
+    out['Qi'] = M.Qi[:, :, lo:hi][:, :, idx]
+    out['ri'] = M.ri[:, lo:hi][:, idx]
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def measure(args, cfg_name, sizes, comm, rank, world, local_rank, on_gpu, custom=False, dump=None):
     """One configuration: workload, Master, `warm` untimed EP iterations, then EXACTLY `steps` timed ones bracketed by
     barrier + device synchronisation on both sides.  Returns (record, Master) on rank 0, (None, Master) elsewhere: every rank
     keeps its Master, because the parity iteration behind the timed region is a collective EP iteration like any other."""
@@ -570,6 +594,8 @@ def measure(args, cfg_name, sizes, comm, rank, world, local_rank, on_gpu, custom
     if rank != 0:
         return None, M
     assert info == 0, 'EP failed with info %d' % info
+    if dump:
+        dump_outputs(dump, res, M)
 
     # dominant kernel: the sampler, timed with HIP events on the library's stream
     ms = np.array(M.sampling_ms[n_launch0:])
@@ -748,7 +774,12 @@ def main():
                     help='skip the C2 / C5-shard records behind the headline (default: measured when the headline is C3 on one GPU)')
     ap.add_argument('--dry-run', action='store_true',
                     help='launch + rendezvous only (no GPU work): checks that --gpus N starts N ranks')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (moments, global and rank 0\'s site '
+                         'parameters) as DIR/<name>.npy, float64, at most 64 MB')
     args = ap.parse_args()
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     sites, D, n, cor, steps, warm = CONFIGS[args.config]
     sites = args.sites if args.sites is not None else sites
     D = args.D if args.D is not None else D
@@ -807,7 +838,7 @@ def main():
 
     sizes = (sites, D, n, cor, steps, warm)
     out, M = measure(args, args.config, sizes, comm, rank, world, local_rank, on_gpu,
-                     custom=(args.sites, args.D, args.n) != (None, None, None))
+                     custom=(args.sites, args.D, args.n) != (None, None, None), dump=args.dump_outputs)
     # ---- behind the timed region.  ORDER MATTERS: the parity iteration is an EP iteration, i.e. it
     # contains the all-reduces of epx_update_trial, so EVERY rank runs it; only behind it do ranks != 0 leave, and from
     # there on rank 0 calls nothing collective (cpu_leg: engine getters, device-local test hooks, the CPU oracle).

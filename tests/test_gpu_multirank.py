@@ -111,11 +111,47 @@ def test_rccl_world_of_one_with_the_real_sampler():
 
 
 # ------------------------------------------------------------------ two processes
-def _worker(rank, world, port, mode, outdir, transport):
+# Rank processes that may hold the device at the same time besides the suite's own: shared GPU hosts cap the processes
+# with a device open (six at once, the suite's own included, on the hosts this suite runs on; eight ranks plus the suite
+# made nine and the run was stopped).  A larger world runs in ONE process,
+# one thread per rank, with an all-reduce through that process's memory (_ThreadWorld) as dist.HostComm's transport:
+# the library's multi-rank code is the same, only the hand-off of each reduction differs.
+MAX_RANK_PROCS = 4
+
+
+class _ThreadWorld(object):
+    """Ranks that are threads of one process: one slot per rank and a barrier."""
+
+    def __init__(self, world, timeout=1800.0):
+        import threading
+        self.world = world
+        self.slots = [None] * world
+        self.barrier = threading.Barrier(world, timeout=timeout)
+
+
+class _ThreadRank(object):
+    """One rank of a _ThreadWorld with the transport interface of dist.HostComm: `reduce` combines the ranks' arrays in
+    rank order, so every rank receives the same bits."""
+
+    def __init__(self, tw, rank):
+        self.tw, self.rank, self.world = tw, rank, tw.world
+
+    def reduce(self, a, op):
+        from epstan_amd import _lib
+        f = {_lib.OP_SUM: np.add, _lib.OP_MIN: np.minimum, _lib.OP_MAX: np.maximum}[op]
+        tw = self.tw
+        tw.slots[self.rank] = np.array(a, dtype=np.float64)
+        tw.barrier.wait()
+        out = tw.slots[0].copy()
+        for x in tw.slots[1:]:
+            out = f(out, x)
+        tw.barrier.wait()                              # no slot is overwritten before every rank has read them all
+        a[...] = out
+
+
+def _worker(proc, world, port, mode, outdir, transport):
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
-    os.environ['RANK'] = str(rank)
-    os.environ['WORLD_SIZE'] = str(world)
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     if transport in ('gloo', 'host'):
         # several PROCESSES on the box's one device: the driver may park a workgroup of a pieced launch that holds a site
@@ -125,9 +161,43 @@ def _worker(rank, world, port, mode, outdir, transport):
     for p in (ROOT, os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'tests', 'golden')):
         if p not in sys.path:
             sys.path.insert(0, p)
+    if world <= MAX_RANK_PROCS:
+        os.environ['RANK'] = str(proc)
+        os.environ['WORLD_SIZE'] = str(world)
+        _rank_worker(proc, world, port, mode, outdir, transport)
+        return
+    # every rank in this process, one thread each (host transport only: all ranks run on device 0)
+    assert transport == 'host' and proc == 0
+    import threading
+    from epstan_amd import _lib
+    _lib.load()                                        # once, before the rank threads
+    tw = _ThreadWorld(world)
+    errors = []
+
+    def run(rank):
+        try:
+            _rank_worker(rank, world, port, mode, outdir, transport, group=_ThreadRank(tw, rank))
+        except BaseException as ex:                    # re-raised by the main thread below
+            errors.append(ex)
+            # every later reduction of the peers fails at once, so each peer's library call returns and its thread ends
+            tw.barrier.abort()
+
+    threads = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:                                  # no rank is left inside a HIP call when the process reports
+        t.join()
+    if errors:
+        raise errors[0]
+
+
+def _rank_worker(rank, world, port, mode, outdir, transport, group=None):
     from epstan_amd import dist, models
     from epstan_amd.method import Master
-    if transport in ('gloo', 'host'):
+    if group is not None:
+        comm = dist.HostComm(group)
+        device = 0
+    elif transport in ('gloo', 'host'):
         import torch.distributed as tdist
         tdist.init_process_group('gloo', rank=rank, world_size=world)
         comm = dist.TorchComm()
@@ -192,7 +262,7 @@ def _worker(rank, world, port, mode, outdir, transport):
     comm.barrier()
     if transport != 'gloo':
         comm.close()
-    if transport in ('gloo', 'host'):
+    if transport in ('gloo', 'host') and group is None:
         import torch.distributed as tdist
         tdist.destroy_process_group()
 
@@ -200,7 +270,8 @@ def _worker(rank, world, port, mode, outdir, transport):
 def _spawn(mode, tmp_path, transport, world=2):
     import torch.multiprocessing as mp
     port = _free_port()
-    mp.spawn(_worker, args=(world, port, mode, str(tmp_path), transport), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, port, mode, str(tmp_path), transport), nprocs=world if world <= MAX_RANK_PROCS else 1,
+             join=True)
     return [np.load(os.path.join(str(tmp_path), 'r%d.npz' % r)) for r in range(world)]
 
 
@@ -329,7 +400,8 @@ def test_c4_at_its_own_size_eight_ranks_on_one_device(tmp_path):
     """BASELINE config C4: J = 4096 sites, D = 32, n_j = 500, sharded over 8 ranks (512 sites each, = C3 per rank), one EP
     iteration with the real sampler -- all eight ranks on the one device of the box, the library's own multi-rank code
     (epx_update_trial: per-rank statistics slots, global site offsets, flag reductions) with every collective handed to
-    gloo: everything that runs on the 8-GPU node except ncclAllReduce itself.  Invariants of the C3-size test on every rank,
+    the host (the ranks are threads of one process, _ThreadWorld): everything that runs on the 8-GPU node except
+    ncclAllReduce itself.  Invariants of the C3-size test on every rank,
     bit-equal replicated Q, r, S, m, and Q = Q0 + the sum over ALL ranks' sites (method.py:1073-1074, 1145;
     experiment/fit.py:326-335)."""
     res = _spawn('c4', tmp_path, 'host', world=8)

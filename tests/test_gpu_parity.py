@@ -920,13 +920,15 @@ def test_multigroup_site_updates_match_oracle(model, D, groups, chains, layout):
     random stream; chains are compared until rounding differences make them part)."""
     X, y, k_lim, g_cnt, g_lim, Oms, mus, d = _group_problem(model, D, groups, 70 + D, tight=300.0)
     eng, Om_dev, mu_dev = _group_engine(model, X, y, k_lim, g_cnt, g_lim, Oms, mus)
-    if layout == 2 and eng.P > 128:
-        pytest.skip('one workgroup per chain holds at most 128 coordinates in registers')
+    # one workgroup per chain holds at most 128 coordinates in registers: the library serves a layout-2 request beyond
+    # that with the lock-step form of multi-group sites (layout 4, D <= 32) or streams it (layout 3), and the draws must
+    # still be the oracle's
+    served = (4 if D <= 32 else 3) if layout == 2 and eng.P > 128 else layout
     K = len(groups)
     seeds = np.arange(K, dtype=np.int64) + 31
     it = 44
     stats, ms = eng.sample_batch(seeds, HipEngine.sampler_opts(chains=chains, iter=it, init='random', layout=layout))
-    assert eng.last_layout() == layout
+    assert eng.last_layout() == served
     draws_o, _, st_o = no.nuts_sites(model, X, y, k_lim, mu_dev, Om_dev, seeds, chains=chains, iter=it,
                                      g_cnt=g_cnt, g_lim=g_lim)
     cs = eng.get_chain_stats(chains)
