@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <algorithm>
 #include <vector>
@@ -84,17 +85,13 @@ int epx_comm_allreduce_dev(epx_ctx *c, double *buf, size_t n, int op);      // e
 static inline int ld_of(int d) { return d | 1; }
 static inline size_t dense_slot_doubles(int d) { return 2 * (size_t)d * ld_of(d) + 4 * (size_t)ld_of(d); }
 
-// LDS or global workspace for `nblocks` concurrent dense blocks
-static int dense_ws(epx_ctx *c, int d, int nblocks, DenseWs *ws, size_t *lds_bytes) {
+// LDS or global workspace (grown in `buf`) for `nblocks` concurrent dense blocks
+static int dense_ws(DevBuf<double> &buf, int d, int nblocks, DenseWs *ws, size_t *lds_bytes) {
     const size_t bytes = dense_slot_doubles(d) * 8;
     if (bytes + 1024 <= LDS_CAP) { ws->use_lds = 1; ws->global = nullptr; *lds_bytes = bytes; return 0; }
     ws->use_lds = 0; *lds_bytes = 0;
-    if (c->dense_ws_slots < (size_t)nblocks) {
-        if (c->dense_ws) (void)hipFree(c->dense_ws);
-        HIPCHK(dalloc(&c->dense_ws, dense_slot_doubles(d) * nblocks));
-        c->dense_ws_slots = nblocks;
-    }
-    ws->global = c->dense_ws;
+    HIPCHK(buf.grow(dense_slot_doubles(d) * nblocks));
+    ws->global = buf;
     return 0;
 }
 
@@ -149,21 +146,19 @@ static int ctx_create(int device, int model, int K_local, int D, const int64_t *
     if (K_local < 1) return fail("K_local must be >= 1");
     if (D < 1) return fail("D must be >= 1");
     HIPCHK(hipSetDevice(device));
-    epx_ctx *c = new epx_ctx();
-    memset((void *)c, 0, sizeof(int) * 6);
+    std::unique_ptr<epx_ctx> c(new epx_ctx());          // (freed with all it holds on every early return)
     c->device = device; c->K = K_local; c->D = D; c->d = d; c->P = P;
     c->gauss = yd != nullptr;
     c->model = c->gauss ? model - EPX_M1A_SG : model;       // the kernels take the b-model id plus the family flag
     model = c->model;
     c->k_lim.assign(k_lim, k_lim + K_local + 1);
     c->N = k_lim[K_local] - k_lim[0];
-    c->n_max = 0;
     for (int k = 0; k < K_local; ++k) {
         const int64_t n = k_lim[k + 1] - k_lim[k];
-        if (n < 1) { delete c; return fail("site %d is empty", k); }
+        if (n < 1) return fail("site %d is empty", k);
         if (n > c->n_max) c->n_max = (int)n;
     }
-    if (k_lim[0] != 0) { delete c; return fail("k_lim[0] must be 0 (rows are rank-local)"); }
+    if (k_lim[0] != 0) return fail("k_lim[0] must be 0 (rows are rank-local)");
     // groups: tiles never straddle two groups, so the tile count of a site depends on them
     c->pg = model == EPX_M1B_SG ? 1 : 1 + D;
     c->multi = g_cnt != nullptr;
@@ -173,18 +168,16 @@ static int ctx_create(int device, int model, int K_local, int D, const int64_t *
         int64_t gi = 0;
         for (int k = 0; k < K_local; ++k) {
             const int ng = g_cnt ? g_cnt[k] : 1;
-            if (ng < 1) { delete c; return fail("site %d has %d groups", k, ng); }
+            if (ng < 1) return fail("site %d has %d groups", k, ng);
             if (ng > c->ng_max) c->ng_max = ng;
             int nt = 0;
             for (int g = 0; g < ng; ++g) {
                 const int64_t lo = g_cnt ? g_lim[gi + g] : k_lim[k], hi = g_cnt ? g_lim[gi + g + 1] : k_lim[k + 1];
-                if (hi <= lo) { delete c; return fail("group %d of site %d is empty", g, k); }
+                if (hi <= lo) return fail("group %d of site %d is empty", g, k);
                 nt += (int)((hi - lo + 15) / 16);
             }
-            if (g_cnt && (g_lim[gi] != k_lim[k] || g_lim[gi + ng] != k_lim[k + 1])) {
-                delete c;
+            if (g_cnt && (g_lim[gi] != k_lim[k] || g_lim[gi + ng] != k_lim[k + 1]))
                 return fail("the groups of site %d do not cover its rows", k);
-            }
             if (nt > c->nt_max) c->nt_max = nt;
             gi += ng;
             g0[k + 1] = (int)gi;
@@ -194,11 +187,6 @@ static int ctx_create(int device, int model, int K_local, int D, const int64_t *
             c->P = d + c->ng_max * c->pg;           // record stride: the largest site
         }
     }
-    c->dense_ws = nullptr; c->dense_ws_slots = 0;
-    c->draws = c->last = c->chain_stats = c->site_stats = c->stack = nullptr; c->team_passes = nullptr;
-    c->seeds_d = nullptr; c->inj = nullptr; c->inj_elems = 0; c->stack_elems = 0;
-    c->s_chains = 0; c->s_nkeep = 0; c->has_last = 0; c->nsamp = 0; c->last_df = 0.0;
-    c->stamps = nullptr; c->stamps_n = 0; c->stamps_last = 0;
     HIPCHK(hipStreamCreate(&c->stream));
     HIPCHK(hipEventCreate(&c->ev0));
     HIPCHK(hipEventCreate(&c->ev1));
@@ -212,62 +200,60 @@ static int ctx_create(int device, int model, int K_local, int D, const int64_t *
     }
     HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    c->split_n = 0; c->last_split = 0;
     {
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, device));
         c->n_cu = prop.multiProcessorCount;
     }
     const size_t K = K_local, d2 = (size_t)d * d;
-    HIPCHK(dalloc(&c->k_lim_d, K + 1));
+    HIPCHK(c->k_lim_d.alloc(K + 1));
     if (c->multi) {
-        HIPCHK(dalloc(&c->site_g0_d, K + 1));
-        HIPCHK(dalloc(&c->g_lim_d, (size_t)g0[K] + 1));
+        HIPCHK(c->site_g0_d.alloc(K + 1));
+        HIPCHK(c->g_lim_d.alloc((size_t)g0[K] + 1));
         HIPCHK(hipMemcpy(c->site_g0_d, g0.data(), (K + 1) * sizeof(int), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(c->g_lim_d, g_lim, ((size_t)g0[K] + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     }
     // X carries a zeroed KiB behind the last row: the streaming sampler's row DMA reads full
     // 128-column images
-    HIPCHK(dalloc(&c->X, (size_t)c->N * D + 128));
+    HIPCHK(c->X.alloc((size_t)c->N * D + 128));
     HIPCHK(hipMemset(c->X + (size_t)c->N * D, 0, 128 * sizeof(double)));
-    HIPCHK(dalloc(&c->y, (size_t)c->N));
-    HIPCHK(dalloc(&c->y32, (size_t)c->N));
-    HIPCHK(dalloc(&c->Q0, d2)); HIPCHK(dalloc(&c->r0, d));
-    HIPCHK(dalloc(&c->Q, d2)); HIPCHK(dalloc(&c->r, d));
-    HIPCHK(dalloc(&c->S, d2)); HIPCHK(dalloc(&c->m, d));
-    HIPCHK(dalloc(&c->Qi, K * d2)); HIPCHK(dalloc(&c->ri, K * d));
-    HIPCHK(dalloc(&c->Qi2, K * d2)); HIPCHK(dalloc(&c->ri2, K * d));
-    HIPCHK(dalloc(&c->dQi, K * d2)); HIPCHK(dalloc(&c->dri, K * d));
+    HIPCHK(c->y.alloc((size_t)c->N));
+    HIPCHK(c->y32.alloc((size_t)c->N));
+    HIPCHK(c->Q0.alloc(d2)); HIPCHK(c->r0.alloc(d));
+    HIPCHK(c->Q.alloc(d2)); HIPCHK(c->r.alloc(d));
+    HIPCHK(c->S.alloc(d2)); HIPCHK(c->m.alloc(d));
+    HIPCHK(c->Qi.alloc(K * d2)); HIPCHK(c->ri.alloc(K * d));
+    HIPCHK(c->Qi2.alloc(K * d2)); HIPCHK(c->ri2.alloc(K * d));
+    HIPCHK(c->dQi.alloc(K * d2)); HIPCHK(c->dri.alloc(K * d));
     // (64 columns of zeros behind the last site's cavity precision: the streaming sampler requests its columns a round
     // ahead, nuts_stream.hip)
-    HIPCHK(dalloc(&c->cav_Om, K * d2 + (size_t)EPX_OM_PAD_COLS * d)); HIPCHK(dalloc(&c->cav_mu, K * d));
+    HIPCHK(c->cav_Om.alloc(K * d2 + (size_t)EPX_OM_PAD_COLS * d)); HIPCHK(c->cav_mu.alloc(K * d));
     HIPCHK(hipMemset(c->cav_Om + K * d2, 0, (size_t)EPX_OM_PAD_COLS * d * sizeof(double)));
-    HIPCHK(dalloc(&c->tilt_mean, K * d)); HIPCHK(dalloc(&c->tilt_scatter, K * d2));
-    HIPCHK(dalloc(&c->flags, K));
-    HIPCHK(dalloc(&c->iflags, 4));
-    HIPCHK(dalloc(&c->min_eig, K));
-    HIPCHK(dalloc(&c->err_flag, 4));
+    HIPCHK(c->tilt_mean.alloc(K * d)); HIPCHK(c->tilt_scatter.alloc(K * d2));
+    HIPCHK(c->flags.alloc(K));
+    HIPCHK(c->iflags.alloc(4));
+    HIPCHK(c->min_eig.alloc(K));
+    HIPCHK(c->err_flag.alloc(4));
     HIPCHK(hipMemset(c->err_flag, 0, 4 * sizeof(int)));
-    HIPCHK(dalloc(&c->dbg, 2 * (size_t)c->P + 1));
-    HIPCHK(dalloc(&c->dbg_seed, 1));
+    HIPCHK(c->dbg.alloc(2 * (size_t)c->P + 1));
+    HIPCHK(c->dbg_seed.alloc(1));
     const int len = 2 * (int)(d2 + d);
     c->nslice = K_local >= 64 ? 32 : 1;
-    HIPCHK(dalloc(&c->packed, (size_t)len + PACKED_EXTRA));
-    HIPCHK(dalloc(&c->partial, (size_t)len * c->nslice));
+    HIPCHK(c->packed.alloc((size_t)len + PACKED_EXTRA));
+    HIPCHK(c->partial.alloc((size_t)len * c->nslice));
     HIPCHK(hipMemcpy(c->k_lim_d, k_lim, (K + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->X, X, (size_t)c->N * D * sizeof(double), hipMemcpyHostToDevice));
-    c->yd = nullptr;
     if (c->gauss) {
         for (int64_t i = 0; i < c->N; ++i)
-            if (!std::isfinite(yd[i])) { epx_ctx_destroy(c); return fail("y[%lld] is not finite", (long long)i); }
-        HIPCHK(dalloc(&c->yd, (size_t)c->N));
+            if (!std::isfinite(yd[i])) return fail("y[%lld] is not finite", (long long)i);
+        HIPCHK(c->yd.alloc((size_t)c->N));
         HIPCHK(hipMemcpy(c->yd, yd, (size_t)c->N * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipMemset(c->y, 0, (size_t)c->N));
         HIPCHK(hipMemset(c->y32, 0, (size_t)c->N * sizeof(int)));
     } else {
         std::vector<uint8_t> yb((size_t)c->N);
         for (int64_t i = 0; i < c->N; ++i) {
-            if (y[i] != 0 && y[i] != 1) { epx_ctx_destroy(c); return fail("y[%lld] = %d is not 0/1", (long long)i, y[i]); }
+            if (y[i] != 0 && y[i] != 1) return fail("y[%lld] = %d is not 0/1", (long long)i, y[i]);
             yb[i] = (uint8_t)y[i];
         }
         HIPCHK(hipMemcpy(c->y, yb.data(), yb.size(), hipMemcpyHostToDevice));
@@ -279,7 +265,7 @@ static int ctx_create(int device, int model, int K_local, int D, const int64_t *
     HIPCHK(hipMemset(c->Q0, 0, d2 * 8)); HIPCHK(hipMemset(c->r0, 0, d * 8));
     HIPCHK(hipMemset(c->Q, 0, d2 * 8)); HIPCHK(hipMemset(c->r, 0, d * 8));
     HIPCHK(hipMemset(c->flags, 0, K));
-    *out = c;
+    *out = c.release();
     return 0;
 }
 
@@ -287,18 +273,6 @@ int epx_ctx_destroy(epx_ctx *c) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
     if (c->comm || c->comm_ext) (void)epx_comm_destroy(c);
-    delete c->dyn_rate_h; c->dyn_rate_h = nullptr;
-    void *ptrs[] = {c->dyn_lens_d, c->ckpt, c->dyn_rate, c->dyn_words, c->carry_eps, c->carry_metric, c->min_eig, c->err_flag, c->comm_stage, c->yd, c->site_g0_d, c->g_lim_d, c->sweep_buf, c->order_d, c->k_lim_d, c->X, c->y, c->y32, c->Q0, c->r0, c->Q, c->r, c->S, c->m, c->Qi, c->ri, c->Qi2,
-                    c->ri2, c->dQi, c->dri, c->cav_Om, c->cav_mu, c->tilt_mean, c->tilt_scatter,
-                    c->flags, c->iflags, c->packed, c->partial, c->dense_ws, c->draws, c->last,
-                    c->chain_stats, c->site_stats, c->stack, c->seeds_d, c->dbg, c->dbg_seed, c->inj, c->trace, c->team_passes};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return 0;
 }
@@ -391,7 +365,7 @@ static int launch_cavity(epx_ctx *c, const double *Qs, const double *rs, const d
     CavityArgs a;
     a.k0 = k0; a.d = c->d; a.ld = ld_of(c->d);
     size_t lds;
-    if (dense_ws(c, c->d, count, &a.ws, &lds)) return -1;
+    if (dense_ws(c->dense_ws, c->d, count, &a.ws, &lds)) return -1;
     a.Q = c->Q; a.r = c->r; a.Qsite = Qs; a.rsite = rs; a.dQsite = dQs; a.drsite = drs;
     a.site_stride = (size_t)c->d * c->d; a.rsite_stride = c->d; a.df = df;
     a.cav_Om = c->cav_Om; a.cav_mu = c->cav_mu; a.flags = c->flags;
@@ -456,57 +430,79 @@ static int norm_opts(const epx_sampler_opts *o, epx_sampler_opts *n) {
 }
 
 static int ensure_sampler_buffers(epx_ctx *c, int chains, int nkeep) {
+    if (c->s_chains == chains && c->s_nkeep == nkeep) return 0;
     const size_t K = c->K, P = c->P;
-    if (c->s_chains != chains || c->s_nkeep != nkeep) {
-        if (c->draws) (void)hipFree(c->draws);
-        if (c->last) (void)hipFree(c->last);
-        if (c->chain_stats) (void)hipFree(c->chain_stats);
-        if (c->site_stats) (void)hipFree(c->site_stats);
-        if (c->seeds_d) (void)hipFree(c->seeds_d);
-        if (c->team_passes) (void)hipFree(c->team_passes);
-        c->draws = c->last = c->chain_stats = c->site_stats = nullptr; c->seeds_d = nullptr; c->team_passes = nullptr;
-        HIPCHK(dalloc(&c->draws, K * chains * nkeep * P));
-        HIPCHK(dalloc(&c->last, K * chains * P));
-        HIPCHK(dalloc(&c->chain_stats, K * chains * ST_COUNT));
-        HIPCHK(dalloc(&c->site_stats, K * 8));
-        HIPCHK(dalloc(&c->team_passes, K));
-        HIPCHK(hipMemset(c->team_passes, 0, K * 8));
-        HIPCHK(dalloc(&c->seeds_d, K));
-        if (c->carry_eps) (void)hipFree(c->carry_eps);
-        if (c->carry_metric) (void)hipFree(c->carry_metric);
-        c->carry_eps = c->carry_metric = nullptr; c->carry_chains = 0;
-        HIPCHK(dalloc(&c->carry_eps, K * chains));
-        HIPCHK(dalloc(&c->carry_metric, K * P));
-        {
-            std::vector<double> neg(K * chains, -1.0);       // no history yet
-            HIPCHK(hipMemcpy(c->carry_eps, neg.data(), neg.size() * 8, hipMemcpyHostToDevice));
-        }
-        HIPCHK(hipMemset(c->last, 0, K * chains * P * 8));
-        HIPCHK(hipMemset(c->chain_stats, 0, K * chains * ST_COUNT * 8));
-        c->s_chains = chains; c->s_nkeep = nkeep; c->has_last = 0;
+    HIPCHK(c->draws.alloc(K * chains * nkeep * P));
+    HIPCHK(c->last.alloc(K * chains * P));
+    HIPCHK(c->chain_stats.alloc(K * chains * ST_COUNT));
+    HIPCHK(c->site_stats.alloc(K * 8));
+    HIPCHK(c->team_passes.alloc(K));
+    HIPCHK(hipMemset(c->team_passes, 0, K * 8));
+    HIPCHK(c->seeds_d.alloc(K));
+    c->carry_chains = 0;
+    HIPCHK(c->carry_eps.alloc(K * chains));
+    HIPCHK(c->carry_metric.alloc(K * P));
+    {
+        std::vector<double> neg(K * chains, -1.0);       // no history yet
+        HIPCHK(hipMemcpy(c->carry_eps, neg.data(), neg.size() * 8, hipMemcpyHostToDevice));
     }
+    HIPCHK(hipMemset(c->last, 0, K * chains * P * 8));
+    HIPCHK(hipMemset(c->chain_stats, 0, K * chains * ST_COUNT * 8));
+    c->s_chains = chains; c->s_nkeep = nkeep; c->has_last = 0;
     return 0;
 }
 
 static int pad_dp(int D) { return D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : D <= 32 ? 32 : -1; }
 
-// layout (out): 1 = one block per site (wave = chain, X resident in LDS), 2 = one block per
-// (site, chain) with 4 cooperating waves, 3 = streaming (chains in lock step, X through an LDS tile)
-static int build_nuts_args(epx_ctx *c, int k0, int count, const epx_sampler_opts &o, NutsArgs &a,
-                           int *wpc_out, int *dp_out, int *nv_out, int *layout_out, int stack_sites = 0) {
-    if (stack_sites < count) stack_sites = count;       // the HBM tree stack is indexed by site: a split launch sizes it for all
-    const int nkeep = (o.iter - o.warmup + o.thin - 1) / o.thin;
+static bool duo_layout(int layout) { return layout == 5 || layout == 6 || layout == 7; }
+
+// The environment switches of a sampling call, read once per call
+struct SamplerEnv {
+    bool piece_grid;          // EPX_PIECE_GRID: a pieced launch runs one workgroup per piece instead of looping ones (A/B)
+    int piece_wait_s;         // EPX_PIECE_WAIT_S: seconds a workgroup of a pieced launch looks for a site
+    int yield_cycles;         // EPX_YIELD: the row team's yield budget (layout 7; A/B: 0 turns it off)
+    bool no_lean;             // EPX_NO_LEAN: layout 7 with the full chain rule in every round (diagnostic)
+    bool test_fail_ckpt;      // EPX_TEST_FAIL_CKPT: the checkpoint records of a pieced launch count as refused (test hook)
+    bool piece_loop;          // EPX_PIECE_LOOP: diagnostic build only, a pieced launch keeps its looping workgroups
+};
+
+static SamplerEnv sampler_env() {
+    const auto num = [](const char *name, int dflt) { const char *s = getenv(name); return s ? atoi(s) : dflt; };
+    SamplerEnv e;
+    e.piece_grid = getenv("EPX_PIECE_GRID") != nullptr;
+    const int wait_s = num("EPX_PIECE_WAIT_S", 0);
+    e.piece_wait_s = wait_s > 0 ? wait_s : EPX_PIECE_WAIT_S;
+    e.yield_cycles = num("EPX_YIELD", EPX_YIELD_DEFAULT);
+    e.no_lean = getenv("EPX_NO_LEAN") != nullptr;
+    e.test_fail_ckpt = getenv("EPX_TEST_FAIL_CKPT") != nullptr;
+    e.piece_loop = getenv("EPX_PIECE_LOOP") != nullptr;
+    return e;
+}
+
+// What the shape and the request decide about a sampler launch
+struct SamplerPlan {
+    int layout, wpc, dp, nv;
+    bool spins;               // the kernel's waves hand off through spins that can give up (NutsArgs::err)
+    NutsArgs a;               // every field but the arrays (bind_sampler) and the form of the launch (run_sampler)
+};
+
+// layout: 1 = one block per site (wave = chain, X resident in LDS), 2 = one block per (site, chain) with 4 cooperating
+// waves, 3 = streaming (chains in lock step, X through an LDS tile), 4 = lock step with the rows resident, 5 / 6 / 7 =
+// row waves + state waves (nuts_duo.hip).  No HIP call, no allocation, no change to the context.
+static int plan_sampler(const epx_ctx &c, int count, const epx_sampler_opts &o, const SamplerEnv &env, SamplerPlan *p) {
+    NutsArgs &a = p->a;
     memset(&a, 0, sizeof a);
     a.dyn_tail_div = 1;                                 // (a divisor: never 0, also for launches that do not come from the piece queue)
-    a.model = c->model; a.D = c->D; a.d = c->d; a.P = c->P; a.k0 = k0;
-    a.gauss = c->gauss; a.yd = c->yd;
-    a.chains = o.chains; a.iter = o.iter; a.warmup = o.warmup; a.thin = o.thin; a.nkeep = nkeep;
+    a.model = c.model; a.D = c.D; a.d = c.d; a.P = c.P;
+    a.gauss = c.gauss;
+    a.chains = o.chains; a.iter = o.iter; a.warmup = o.warmup; a.thin = o.thin; a.nkeep = (o.iter - o.warmup + o.thin - 1) / o.thin;
     a.max_depth = o.max_depth; a.init_mode = o.init;
-    a.k_lim = c->k_lim_d; a.X = c->X; a.y = c->y; a.y32 = c->y32; a.cav_Om = c->cav_Om; a.cav_mu = c->cav_mu;
-    a.site_g0 = c->site_g0_d; a.g_lim = c->g_lim_d; a.ngmax = c->ng_max; a.ntmax = c->nt_max;
+    a.ngmax = c.ng_max; a.ntmax = c.nt_max;
     const int no_spec = o.reserved & 1;           // flag: bookkeeping on the gradient waves (A/B and tests)
-    int nv = (c->P + 63) / 64;
-    int dp = pad_dp(c->D);
+    const int nv = (c.P + 63) / 64;
+    int dp = pad_dp(c.D);
+    p->nv = nv;
+    p->spins = false;
     // resident layouts: enough sites to fill the 256 CUs -> one block per site, else one block
     // per (site, chain) with 4 cooperating waves
     int layout = o.layout;
@@ -515,10 +511,10 @@ static int build_nuts_args(epx_ctx *c, int k0, int count, const epx_sampler_opts
     // cross-over at the C2 site size, where two layout-2 workgroups share a CU (scripts/tick_occupancy.py:
     // layout 2 ahead by 24 % at 192 sites, 5 % at 256, behind by 4 % at 512); 192 when only one fits.
     bool many = count >= 192;
-    if (layout == 0 && !c->multi && dp > 0 && nv <= 2) {
+    if (layout == 0 && !c.multi && dp > 0 && nv <= 2) {
         NutsArgs t = a;
         t.cpb = 1;
-        const size_t lds2 = nuts_lds_layout(t, 4, dp, c->n_max);
+        const size_t lds2 = nuts_lds_layout(t, 4, dp, c.n_max);
         if (2 * lds2 <= LDS_CAP) many = count >= 320;
     }
     // layout 4: one block per site, chains in lock step, rows resident in LDS, MFMA products: the
@@ -528,28 +524,29 @@ static int build_nuts_args(epx_ctx *c, int k0, int count, const epx_sampler_opts
     bool lock = false;
     // several groups per site: one workgroup per chain, the four gradient waves share the
     // site's groups (nuts_gradient_groups.inc); needs rows, Omega, tree stack and mailbox in LDS
+    // (an attempt that does not fit leaves its LDS offsets in `a`: the forms below lay out their own)
     bool grp = false;
-    if (c->multi && dp > 0 && nv <= 2 && !no_spec &&
+    if (c.multi && dp > 0 && nv <= 2 && !no_spec &&
         (layout == 2 || layout == 0)) {       // measured ahead of the lock-step layouts from 32 to 1024 sites (scripts/ab_kj.py)
         a.grp = 1; a.cpb = 1;
-        const size_t lds = nuts_lds_layout(a, 4, dp, c->n_max);
+        const size_t lds = nuts_lds_layout(a, 4, dp, c.n_max);
         if (lds <= LDS_CAP && a.om_in_lds && a.stack_in_lds && a.off_spec > 0) grp = true;
         else a.grp = 0;
     }
     if (grp) {
-        *wpc_out = 4; *dp_out = dp; *nv_out = nv; *layout_out = 2;
         a.no_spec = 0;
+        p->wpc = 4; p->dp = dp; p->layout = 2;
         return 0;
     }
     // (Gaussian-likelihood sites that do not fit the resident forms above are streamed: layout 3)
-    if (layout == 2 && c->multi) layout = 0;
-    if ((layout == 4 || (layout == 0 && c->multi)) && c->D <= 32 && nv <= 7 && !c->gauss) {
-        const int dpl = c->D <= 16 ? 16 : 32;
-        size_t lds = nuts_stream_lds_bytes(nv, dpl, c->d, c->ng_max, c->nt_max, c->n_max, 0);
+    if (layout == 2 && c.multi) layout = 0;
+    if ((layout == 4 || (layout == 0 && c.multi)) && c.D <= 32 && nv <= 7 && !c.gauss) {
+        const int dpl = c.D <= 16 ? 16 : 32;
+        size_t lds = nuts_stream_lds_bytes(nv, dpl, c.d, c.ng_max, c.nt_max, c.n_max, 0);
         if (lds <= LDS_CAP) {
             lock = true; layout = 4; dp = dpl;
-            a.cpb = 4; a.n_max = c->n_max; a.stack_in_lds = 0; a.om_in_lds = 0;
-            const size_t om = (size_t)c->d * c->d * 8;
+            a.cpb = 4; a.n_max = c.n_max; a.stack_in_lds = 0; a.om_in_lds = 0;
+            const size_t om = (size_t)c.d * c.d * 8;
             if (lds + om <= LDS_CAP) { a.om_in_lds = 1; lds += om; }       // small sites: Omega next to the rows
             a.lds_bytes = (int)lds;
         }
@@ -560,8 +557,8 @@ static int build_nuts_args(epx_ctx *c, int k0, int count, const epx_sampler_opts
     // Few sites, models with per-coefficient scales (m4b / m5b): layout 6 by default -- its state wave runs from the
     // "view" alone (nuts_duo.hip), 374 against 413 ms per C2 iteration of layout 2; the other models stay on layout 2
     // (only when every chain has a CU of its own: the regime where a launch is as long as its slowest chain)
-    const bool auto6 = layout == 0 && !many && c->model >= EPX_M4B_SG && count * o.chains <= c->n_cu;
-    if (!lock && !c->multi && !c->gauss && dp > 0 && nv <= 2 && !no_spec &&
+    const bool auto6 = layout == 0 && !many && c.model >= EPX_M4B_SG && count * o.chains <= c.n_cu;
+    if (!lock && !c.multi && !c.gauss && dp > 0 && nv <= 2 && !no_spec &&
         (layout == 5 || layout == 6 || layout == 7 || (layout == 0 && many) || auto6)) {
         // layout 7: the row TEAM of nuts_duo.hip -- four row waves serve the four chains of a site in lock step on the
         // matrix pipe, the state waves are layout 5's; the default for batches that fill the chip since round 3 (layout 5
@@ -574,42 +571,31 @@ static int build_nuts_args(epx_ctx *c, int k0, int count, const epx_sampler_opts
             const bool six = cand[ic] == 6, seven = cand[ic] == 7;
             const int cpb = six ? 1 : 4, rw = six ? 2 : (seven ? 4 : 1);
             NutsArgs t = a;
-            const size_t lds = nuts_duo_lds_layout(t, cpb, rw, dp, c->n_max);
+            const size_t lds = nuts_duo_lds_layout(t, cpb, rw, dp, c.n_max);
             // (layout 6: one chain per workgroup, the bookkeeping wave's stack lives in LDS or the layout is not used)
             const bool fits = nuts_duo_has(cpb, rw, dp, nv) && lds <= LDS_CAP &&
-                              (seven ? (c->n_max + 63) / 64 <= 32 : (c->n_max + 64 * rw - 1) / (64 * rw) <= 64) &&
+                              (seven ? (c.n_max + 63) / 64 <= 32 : (c.n_max + 64 * rw - 1) / (64 * rw) <= 64) &&
                               (!six || t.stack_in_lds);
             if (!fits) continue;
             a = t;
-            a.err = c->err_flag;
-            layout = cand[ic];
-            {
-                a.stack_stride = nuts_resident_chain_doubles(nv, o.max_depth);
-                const size_t need = (size_t)stack_sites * o.chains * a.stack_stride;
-                if (c->stack_elems < need) {
-                    if (c->stack) (void)hipFree(c->stack);
-                    HIPCHK(dalloc(&c->stack, need));
-                    c->stack_elems = need;
-                }
-                a.stack = c->stack;
-            }
-            a.no_spec = seven && getenv("EPX_NO_LEAN") ? 1 : 0;       // (diagnostic: layout 7 with the full chain rule in every round)
-            { const char *y = getenv("EPX_YIELD"); a.yield_cycles = seven ? (y ? atoi(y) : EPX_YIELD_DEFAULT) : 0; }      // (A/B: EPX_YIELD=0 turns it off)
-            *wpc_out = rw; *dp_out = dp; *nv_out = nv; *layout_out = layout;
+            a.stack_stride = nuts_resident_chain_doubles(nv, o.max_depth);
+            a.no_spec = seven && env.no_lean;                   // (diagnostic: layout 7 with the full chain rule in every round)
+            a.yield_cycles = seven ? env.yield_cycles : 0;
+            p->wpc = rw; p->dp = dp; p->layout = cand[ic]; p->spins = true;
             return 0;
         }
         if (layout == 5 || layout == 6 || layout == 7) layout = 0;
     }
     if (layout == 0) layout = many ? 1 : 2;
     int wpc = 1;
-    bool resident = !lock && dp > 0 && nv <= 2 && layout != 3 && !c->multi;      // several groups per site: layouts 3 / 4 only
+    bool resident = !lock && dp > 0 && nv <= 2 && layout != 3 && !c.multi;      // several groups per site: layouts 3 / 4 only
     if (resident) {
         if (layout == 1) { wpc = 1; a.cpb = o.chains < 4 ? o.chains : 4; }
         else { wpc = 4; a.cpb = 1; }
-        const size_t lds = nuts_lds_layout(a, wpc, dp, c->n_max);
+        const size_t lds = nuts_lds_layout(a, wpc, dp, c.n_max);
         if (lds > LDS_CAP) resident = false;
     }
-    if (c->gauss) {
+    if (c.gauss) {
         // Gaussian-likelihood family: the resident kernels are built for their everything-in-LDS forms; any other
         // shape (rows beyond the LDS, D > 32, several groups with many coordinates) is streamed (layout 3)
         const bool ok = resident && a.om_in_lds && (wpc == 1 || (a.stack_in_lds && a.off_spec > 0 && !no_spec));
@@ -618,35 +604,127 @@ static int build_nuts_args(epx_ctx *c, int k0, int count, const epx_sampler_opts
     if (!resident && !lock) {
         // rows (or parameters) do not fit the resident kernel: stream X through an LDS tile
         layout = 3;
-        if (c->D > 128) return fail("D = %d > 128 is not supported by the streaming sampler", c->D);
-        if (nv > 7) return fail("P = %d > 448 sampled coordinates not supported", c->P);
-        dp = c->D <= 64 ? 64 : 128;
+        if (c.D > 128) return fail("D = %d > 128 is not supported by the streaming sampler", c.D);
+        if (nv > 7) return fail("P = %d > 448 sampled coordinates not supported", c.P);
+        dp = c.D <= 64 ? 64 : 128;
         a.cpb = 4; wpc = 1;
         a.stack_in_lds = 0; a.om_in_lds = 0;
-        a.lds_bytes = (int)nuts_stream_lds_bytes(nv, dp, c->d, c->ng_max, c->nt_max, 0, c->gauss);
+        a.lds_bytes = (int)nuts_stream_lds_bytes(nv, dp, c.d, c.ng_max, c.nt_max, 0, c.gauss);
         a.off_piece = a.lds_bytes; a.lds_bytes += 16;       // (site, first transition) of a pieced launch's workgroup
-        a.err = c->err_flag;
+        p->spins = true;
         if ((size_t)a.lds_bytes > LDS_CAP) return fail("streaming sampler needs %d B of LDS", a.lds_bytes);
     }
-    if (!a.stack_in_lds) {
+    if (!a.stack_in_lds)
         a.stack_stride = layout >= 3 ? nuts_stream_chain_doubles(nv, o.max_depth) : nuts_resident_chain_doubles(nv, o.max_depth);
-        const size_t need = (size_t)stack_sites * o.chains * a.stack_stride;
-        if (c->stack_elems < need) {
-            if (c->stack) (void)hipFree(c->stack);
-            HIPCHK(dalloc(&c->stack, need));
-            c->stack_elems = need;
-        }
-        a.stack = c->stack;
-    }
     a.no_spec = no_spec;
-    *wpc_out = wpc; *dp_out = dp; *nv_out = nv; *layout_out = layout;
+    p->wpc = wpc; p->dp = dp; p->layout = layout;
     return 0;
 }
 
-static int launch_sampler(const NutsArgs &a, int count, int wpc, int dp, int nv, int layout, hipStream_t stream) {
-    if (layout == 5 || layout == 6 || layout == 7) return launch_nuts_duo(a, count, a.cpb, a.duo_rw, dp, nv, stream);
-    if (layout >= 3) return launch_nuts_stream(a, count, dp, nv, stream);
-    return launch_nuts(a, count, wpc, dp, nv, stream);
+// The context's arrays into the arguments of a planned launch.  Called once every buffer of the call has its size:
+// nothing is re-allocated behind it.
+static NutsArgs bind_sampler(const epx_ctx &c, int k0, const SamplerPlan &p) {
+    NutsArgs a = p.a;
+    a.k0 = k0;
+    a.k_lim = c.k_lim_d; a.X = c.X; a.y = c.y; a.y32 = c.y32; a.yd = c.yd; a.cav_Om = c.cav_Om; a.cav_mu = c.cav_mu;
+    a.site_g0 = c.site_g0_d; a.g_lim = c.g_lim_d;
+    if (p.spins) a.err = c.err_flag;
+    if (a.stack_stride) a.stack = c.stack;                              // (tree stack + cold store in global memory)
+    return a;
+}
+
+static int launch_sampler(const SamplerPlan &p, const NutsArgs &a, int count, hipStream_t stream) {
+    if (duo_layout(p.layout)) return launch_nuts_duo(a, count, a.cpb, a.duo_rw, p.dp, p.nv, stream);
+    if (p.layout >= 3) return launch_nuts_stream(a, count, p.dp, p.nv, stream);
+    return launch_nuts(a, count, p.wpc, p.dp, p.nv, stream);
+}
+
+// Piece queue (epx_set_piece_queue): one workgroup per piece, sites claimed by largest remaining predicted work.  The
+// test hook epx_sample_piece runs ONE transition per site from injected checkpoint records the same way.
+struct PieceQueue {
+    bool on = false;
+    int len = 0;              // nominal transitions of a piece
+    int tail_div = 1;         // the pieces behind 3/4 of a site's run are len / tail_div long (epx_pieces.h)
+    int nb_site = 0;          // piece boundaries (checkpoint records) per site
+    int nwg = 0;              // workgroups: at most one per piece (looping ones: the launcher cuts it to what the device holds)
+    bool looping = false;     // the workgroups loop over claims instead of running one piece each
+    size_t stack_elems = 0, ckpt_elems = 0;
+};
+
+static PieceQueue plan_queue(const epx_ctx &c, int k0, int count, const epx_sampler_opts &o, const SamplerPlan &p,
+                             const SamplerEnv &env, bool fixed_steps) {
+    PieceQueue q;
+    const bool hook = c.hook_t0 > 0;
+    q.on = (c.dyn_len > 0 || hook) && (p.layout == 5 || p.layout == 7 || p.layout == 3) && k0 == 0 && count == c.K &&
+           o.chains <= p.a.cpb && !fixed_steps && (o.layout == 0 || o.layout == p.layout);
+    if (!q.on) return q;
+    q.len = hook ? 1 : c.dyn_len;
+    // Shorter pieces behind 3/4 of a site's run (epx_pieces.h): a quarter of the nominal length for the STREAMING sampler
+    // (layout 3; same-box A/B at the C5 shard: +0.7 %, profiles/r05_piece_tail_ab.txt), one length throughout for the resident
+    // layouts -- there a piece start re-stages the site's 128 KB of rows, the A/B showed no gain (546.6 / 545.9 / 545.6 /
+    // 545.8 site-updates/s) and the extra pieces cost 7 GB of HBM traffic per C3 launch.
+    q.tail_div = p.layout == 3 ? 4 : 1;
+    const int np = piece_boundaries(o.iter, q.len, q.tail_div);     // (nominal pieces, then shorter ones behind 3/4 of the run)
+    const size_t pieces = (size_t)count * np;
+    q.nb_site = np + 1;
+    // (the hook: `count` workgroups of the one-piece-per-workgroup form claim one site each and run ONE transition)
+    q.nwg = hook ? count : (int)pieces;
+    q.looping = !env.piece_grid && !hook;
+#ifdef EPX_STAMPS
+    if (!env.piece_loop) q.looping = false;     // (the diagnostic build's records are per workgroup: one piece each unless asked otherwise)
+#endif
+    // A pieced launch keeps tree stack + cold store per WORKGROUP (1 GB at the C5 shard; 4 GB with one region per piece)
+    // and a checkpoint record per piece boundary.  (Looping workgroups keep theirs per RESIDENT workgroup: never more than
+    // 8 per CU; with one workgroup per piece, EPX_PIECE_GRID, every piece has its own.)
+    const size_t regions = (q.looping && pieces > (size_t)c.n_cu * 8) ? (size_t)c.n_cu * 8 : pieces;
+    q.stack_elems = regions * o.chains * p.a.stack_stride;
+    q.ckpt_elems = (size_t)count * q.nb_site * o.chains * piece_record_doubles(p.nv);
+    return q;
+}
+
+// the queue's words and checkpoint records into the launch (behind the allocations)
+static int bind_queue(epx_ctx *c, const PieceQueue &q, int count, const epx_sampler_opts &o, const SamplerEnv &env, int nv,
+                      NutsArgs *a) {
+    const bool hook = c->hook_t0 > 0;
+    HIPCHK(hipMemsetAsync(c->dyn_words, 0, 2 * (size_t)count * sizeof(int), c->stream));      // (stream-ordered in front of the launch)
+    a->dyn_prog = c->dyn_words; a->dyn_busy = c->dyn_words + count;
+    a->dyn_rate = (c->dyn_has_rate && !hook) ? c->dyn_rate.p : nullptr;
+    a->dyn_len = q.len; a->dyn_count = count; a->dyn_hook = hook;
+    a->dyn_wait_s = env.piece_wait_s;
+    a->dyn_nb = q.nb_site; a->dyn_tail_div = q.tail_div;
+    a->seg_nwg = q.nwg; a->persist = q.looping;
+    a->ckpt = c->ckpt;                                   // (one record per piece boundary of a site)
+    a->order = nullptr;
+    if (hook) {
+        // every site stands at transition t0 with the caller's records at that boundary; the piece leaves the record of
+        // boundary t0 + 1
+        std::vector<int> prog((size_t)count, 2 * c->hook_t0);
+        HIPCHK(hipStreamSynchronize(c->stream));        // (the memset above is stream-ordered, this copy is not)
+        HIPCHK(hipMemcpy(c->dyn_words, prog.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice));
+        const size_t rec = piece_record_doubles(nv);
+        for (int k = 0; k < count; ++k)
+            HIPCHK(hipMemcpy(c->ckpt + (((size_t)k * q.nb_site + c->hook_t0) * o.chains) * rec,
+                             c->hook_in + (size_t)k * o.chains * rec, (size_t)o.chains * rec * 8, hipMemcpyHostToDevice));
+    }
+    c->last_segments = -((o.iter + q.len - 1) / q.len);      // (negative: pieces per site of a queued launch, at the nominal length)
+    return 0;
+}
+
+// Split launch (epx_set_site_split): the leading sites of the order -- the ones expected to need the most leapfrogs --
+// run one workgroup per chain (layout 2, shorter leapfrog) on a second queue while the rest run one workgroup per site
+// (layout 1, more chains per CU).  The launch ends with its slowest chain; this takes that chain at the faster tick.
+// Returns the number of lead sites (0: no split), -1 on an error.
+static int plan_split(const epx_ctx &c, int count, const epx_sampler_opts &o, const SamplerEnv &env, const SamplerPlan &p,
+                      SamplerPlan *lead) {
+    if (o.layout != 0 || !(p.layout == 1 || p.layout == 5 || p.layout == 7) || c.split_n <= 0) return 0;
+    int n_lead = c.split_n < count ? c.split_n : count - 1;
+    const int cap = c.n_cu / (2 * o.chains);          // at most half of the CUs for the lead sites
+    if (n_lead > cap) n_lead = cap;
+    if (n_lead <= 0) return 0;
+    epx_sampler_opts o2 = o;
+    o2.layout = 2;
+    if (plan_sampler(c, n_lead, o2, env, lead)) return -1;
+    return lead->layout == 2 ? n_lead : 0;
 }
 
 static int run_sampler(epx_ctx *c, int k0, int count, const int64_t *seeds, const epx_sampler_opts &o,
@@ -655,204 +733,97 @@ static int run_sampler(epx_ctx *c, int k0, int count, const int64_t *seeds, cons
     const int nkeep = (o.iter - o.warmup + o.thin - 1) / o.thin;
     if (ensure_sampler_buffers(c, o.chains, nkeep)) return -1;
     if (o.init == EPX_INIT_PREV && !c->has_last) return fail("init=PREV before any sampling call");
-    NutsArgs a;
-    int wpc, dp, nv, layout;
-    if (build_nuts_args(c, k0, count, o, a, &wpc, &dp, &nv, &layout)) return -1;
-    a.seeds = c->seeds_d; a.draws = c->draws; a.last = c->last; a.chain_stats = c->chain_stats;
-    a.eps_in = eps_dev; a.inv_e_in = inv_e_dev; a.t_offset = t_offset;
-    a.team_passes = c->team_passes;
-    HIPCHK(hipMemsetAsync(c->team_passes + k0, 0, (size_t)count * 8, c->stream));
-    const bool want_carry = (o.reserved & 2) != 0 && !eps_dev;
-    if (want_carry) { a.carry_eps = c->carry_eps; a.carry_metric = c->carry_metric; }
-    a.order = (c->order_d && c->order_n == count && k0 == 0) ? c->order_d : nullptr;
+    const SamplerEnv env = sampler_env();
+    const bool hook = c->hook_t0 > 0;          // epx_sample_piece
+    const int *order = (c->order_d && c->order_n == count && k0 == 0) ? c->order_d.p : nullptr;
+
+    // 1. plan the launch, and the lead part of a split launch (it runs when the launch is not pieced)
+    SamplerPlan p, lead;
+    if (plan_sampler(*c, count, o, env, &p)) return -1;
     c->last_segments = 0;
     c->trace_chains = 0;
-    if (c->trace_sites > 0 && !eps_dev) {
-        // test hook (epx_set_trace): a record of every transition of the first sites' chains, warm-up included
-        const int ts = c->trace_sites < count ? c->trace_sites : count;
-        const size_t need = (size_t)ts * o.chains * o.iter * (size_t)(8 + c->P);
-        if (c->trace_n < need) {
-            if (c->trace) (void)hipFree(c->trace);
-            c->trace = nullptr; c->trace_n = 0;
-            HIPCHK(dalloc(&c->trace, need));
-            c->trace_n = need;
-        }
-        HIPCHK(hipMemsetAsync(c->trace, 0, need * 8, c->stream));
-        a.trace = c->trace; a.trace_sites = ts;
-        c->trace_chains = o.chains; c->trace_iter = o.iter; c->trace_last_sites = ts;
-    }
-    // Piece queue (epx_set_piece_queue): one workgroup per piece, sites claimed by largest remaining predicted work
-    const bool hook = c->hook_t0 > 0;          // epx_sample_piece: ONE transition per site from injected checkpoint records
-    bool use_queue = (c->dyn_len > 0 || hook) && (layout == 5 || layout == 7 || layout == 3) && k0 == 0 && count == c->K &&
-                     o.chains <= a.cpb && !eps_dev && !a.dbg && (o.layout == 0 || o.layout == layout);
-    if (hook && (!use_queue || c->hook_t0 >= o.iter))
-        return fail("epx_sample_piece: needs a piece-capable layout (5, 7, 3; got %d) over all sites and 0 < t0 < iter", layout);
-    // Piece lengths are per site.  Default: piece_len transitions for every site.  With EPX_EQUAL_WORK_PIECES set (A/B only)
-    // a site gets pieces of  piece_len x (mean rate / its rate)  transitions, within [piece_len / 4, 4 piece_len], so that
-    // the workgroups of the launch last about equally long -- tried against the 10 % of idle CUs that the piece timeline of
-    // a C5-shard launch shows (profiles/r03_stream_piece_timeline.json) and measured SLOWER (54.6 % against 58.1 % of the
-    // HBM peak: more pieces re-prime more often and the light sites' long pieces coarsen the end of the launch); kept off.
-    std::vector<int> lens_h;
-    // Shorter pieces behind 3/4 of a site's run (epx_pieces.h): a quarter of the nominal length for the STREAMING sampler
-    // (layout 3; same-box A/B at the C5 shard: +0.7 %, profiles/r05_piece_tail_ab.txt), one length throughout for the resident
-    // layouts -- there a piece start re-stages the site's 128 KB of rows, the A/B showed no gain (546.6 / 545.9 / 545.6 /
-    // 545.8 site-updates/s) and the extra pieces cost 7 GB of HBM traffic per C3 launch.  EPX_PIECE_TAIL_DIV overrides (A/B).
-    int tail_div = layout == 3 ? 4 : 1;
-    if (const char *tde = getenv("EPX_PIECE_TAIL_DIV")) { const int v = atoi(tde); tail_div = v > 1 ? v : 1; }
-    size_t total_pieces = 0;
-    int nb_site = 0;
-    if (use_queue) {
-        lens_h.assign((size_t)count, hook ? 1 : c->dyn_len);
-        if (!hook && getenv("EPX_EQUAL_WORK_PIECES") && c->dyn_has_rate && c->dyn_rate_h && (int)c->dyn_rate_h->size() >= count) {
-            double mean = 0.0;
-            for (int k = 0; k < count; ++k) mean += (*c->dyn_rate_h)[k];
-            mean /= count;
-            const int lo = c->dyn_len / 4 > 1 ? c->dyn_len / 4 : 1, hi = 4 * c->dyn_len;
-            for (int k = 0; k < count; ++k) {
-                int l = (int)std::lround(c->dyn_len * mean / (*c->dyn_rate_h)[k]);
-                l = l < lo ? lo : (l > hi ? hi : l);
-                lens_h[k] = l > o.iter ? o.iter : l;
-            }
-        }
-        for (int k = 0; k < count; ++k) {
-            const int np = piece_boundaries(o.iter, lens_h[k], tail_div);     // (nominal pieces, then shorter ones behind 3/4 of the run: epx_pieces.h)
-            total_pieces += np;
-            nb_site = np + 1 > nb_site ? np + 1 : nb_site;
-        }
-    }
-    if (use_queue) {
-        // A pieced launch keeps tree stack + cold store per WORKGROUP (1 GB at the C5 shard; 4 GB with one region per piece)
-        // and a checkpoint record per piece boundary.  If the device cannot give that memory, the launch runs unpieced -- same
-        // draws, one workgroup per site -- instead of failing the sampling call.
-        // (looping workgroups -- the default -- keep theirs per RESIDENT workgroup: never more than 8 per CU; with one
-        // workgroup per piece, EPX_PIECE_GRID, every piece has its own)
-        bool looping = !getenv("EPX_PIECE_GRID") && !hook;
 #ifdef EPX_STAMPS
-        if (!getenv("EPX_PIECE_LOOP")) looping = false;     // (the diagnostic build's records are per workgroup: one piece each unless asked otherwise)
+    const bool may_split = false;       // (the diagnostic build's records are per workgroup of ONE launch)
+#else
+    const bool may_split = order && !eps_dev;
 #endif
-        const size_t regions = (looping && total_pieces > (size_t)c->n_cu * 8) ? (size_t)c->n_cu * 8 : total_pieces;
-        const size_t need_stack = regions * o.chains * a.stack_stride;
-        const size_t need_ckpt = (size_t)count * nb_site * o.chains * (size_t)(4 * nv + 1) * 64;
-        if (c->stack_elems < need_stack) {
-            double *p = nullptr;
-            if (dalloc(&p, need_stack) == hipSuccess) {
-                if (c->stack) (void)hipFree(c->stack);
-                c->stack = p; c->stack_elems = need_stack;
-            } else { (void)hipGetLastError(); use_queue = false; }
-        }
-        if (use_queue && c->ckpt_n < need_ckpt) {
-            double *p = nullptr;
-            // (EPX_TEST_FAIL_CKPT: the test hook of this fallback -- the allocation counts as refused)
-            if (!getenv("EPX_TEST_FAIL_CKPT") && dalloc(&p, need_ckpt) == hipSuccess) {
-                if (c->ckpt) (void)hipFree(c->ckpt);
-                c->ckpt = p; c->ckpt_n = need_ckpt;
-            } else { (void)hipGetLastError(); use_queue = false; }
-        }
-        // (build_nuts_args took c->stack before the re-allocation above: the launch -- pieced or, when the checkpoint records
-        // could not be had, unpieced -- must see the buffer that exists now.  The larger buffer also serves the unpieced form.)
-        a.stack = c->stack;
-    }
+    int n_lead = 0;
+    if (may_split && (n_lead = plan_split(*c, count, o, env, p, &lead)) < 0) return -1;
+    // 2. the piece queue
+    PieceQueue q = plan_queue(*c, k0, count, o, p, env, eps_dev != nullptr);
+    if (hook && (!q.on || c->hook_t0 >= o.iter))
+        return fail("epx_sample_piece: needs a piece-capable layout (5, 7, 3; got %d) over all sites and 0 < t0 < iter", p.layout);
+    // 3. sizes.  The tree stack is indexed by site of the batch: the two launches of a split share it
+    const size_t stride = std::max(p.a.stack_stride, n_lead ? lead.a.stack_stride : (size_t)0);
+    const size_t stack_elems = (size_t)count * o.chains * stride;
+    const int ts = (c->trace_sites > 0 && !eps_dev) ? std::min(c->trace_sites, count) : 0;     // (test hook epx_set_trace)
+    const size_t trace_elems = (size_t)ts * o.chains * o.iter * (size_t)(8 + c->P);
+    // 4. grow.  If the device cannot give the pieced launch its memory, the launch runs unpieced -- same draws, one
+    // workgroup per site -- instead of failing the sampling call (EPX_TEST_FAIL_CKPT: the test hook of that fallback)
+    if (q.on && !(c->stack.try_grow(std::max(stack_elems, q.stack_elems)) &&
+                  (env.test_fail_ckpt ? c->ckpt.n >= q.ckpt_elems : c->ckpt.try_grow(q.ckpt_elems))))
+        q.on = false;
     // (the hook has no unpieced form: if the records could not be had, the call fails instead of running a whole update
     // and copying out of a checkpoint buffer that is missing or too small)
-    if (hook && !use_queue) return fail("epx_sample_piece: the checkpoint records / tree stacks of the pieced launch could not be allocated");
-    if (use_queue) {
-        if (!c->dyn_words) HIPCHK(dalloc(&c->dyn_words, 2 * (size_t)c->K));
-        HIPCHK(hipMemsetAsync(c->dyn_words, 0, 2 * (size_t)count * sizeof(int), c->stream));      // (stream-ordered in front of the launch)
-        a.dyn_prog = c->dyn_words; a.dyn_busy = c->dyn_words + count;
-        a.dyn_rate = (c->dyn_has_rate && !hook) ? c->dyn_rate : nullptr;
-        a.dyn_len = hook ? 1 : c->dyn_len; a.dyn_count = count;
-        a.dyn_hook = hook ? 1 : 0;
-        a.dyn_wait_s = EPX_PIECE_WAIT_S;
-        if (const char *we = getenv("EPX_PIECE_WAIT_S")) { const int v = atoi(we); if (v > 0) a.dyn_wait_s = v; }
-        if (!c->dyn_lens_d) HIPCHK(dalloc(&c->dyn_lens_d, (size_t)c->K));
-        HIPCHK(hipMemcpyAsync(c->dyn_lens_d, lens_h.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));            // (lens_h is a local)
-        a.dyn_lens = c->dyn_lens_d; a.dyn_nb = nb_site; a.dyn_tail_div = tail_div;
-        a.seg_nwg = (int)total_pieces;                      // at most one workgroup per piece ...
-        a.persist = getenv("EPX_PIECE_GRID") ? 0 : 1;       // ... looping ones, as many as the device holds (the launcher cuts seg_nwg down); EPX_PIECE_GRID: the first form, for A/B
-        if (hook) {
-            // every site stands at transition t0 with the caller's records at that boundary; `count` workgroups of the
-            // one-piece-per-workgroup form claim one site each, run ONE transition, leave the record of boundary t0 + 1
-            a.seg_nwg = count; a.persist = 0;
-            std::vector<int> prog((size_t)count, 2 * c->hook_t0);
-            HIPCHK(hipStreamSynchronize(c->stream));        // (the memset above is stream-ordered, this copy is not)
-            HIPCHK(hipMemcpy(c->dyn_words, prog.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice));
-            const size_t rec = (size_t)(4 * nv + 1) * 64;
-            for (int k = 0; k < count; ++k)
-                HIPCHK(hipMemcpy(c->ckpt + (((size_t)k * nb_site + c->hook_t0) * o.chains) * rec,
-                                 c->hook_in + (size_t)k * o.chains * rec, (size_t)o.chains * rec * 8, hipMemcpyHostToDevice));
-        }
+    if (hook && !q.on) return fail("epx_sample_piece: the checkpoint records / tree stacks of the pieced launch could not be allocated");
+    if (q.on) n_lead = 0;
+    HIPCHK(c->stack.grow(stack_elems));
+    if (q.on) HIPCHK(c->dyn_words.grow(2 * (size_t)c->K));
+    if (ts) HIPCHK(c->trace.grow(trace_elems));
 #ifdef EPX_STAMPS
-        if (!getenv("EPX_PIECE_LOOP")) a.persist = 0;       // (the diagnostic build's records are per workgroup: one piece each unless asked otherwise)
+    // (per workgroup three records of 8 sums: the roles' shares, then the phases of the row team's pass; behind them two
+    // records of the first diagnostic form and six of histograms.  A pieced launch: one workgroup per piece)
+    const int nblk = q.on ? q.nwg : count * ((o.chains + p.a.cpb - 1) / p.a.cpb);
+    const size_t stamp_recs = (size_t)3 * nblk + 8;
+    HIPCHK(c->stamps.grow(stamp_recs * 8));
 #endif
-        a.stack = c->stack;                                  // (tree stack + cold store: one region per piece, sized above)
-        a.ckpt = c->ckpt;                                    // (one record per piece boundary of a site)
-        a.order = nullptr;
-        { const int nominal = hook ? 1 : c->dyn_len; c->last_segments = -((o.iter + nominal - 1) / nominal); }      // (negative: pieces per site of a queued launch, at the nominal length)
-    }
-    // Split launch (epx_set_site_split): the leading sites of the order -- the ones expected to
-    // need the most leapfrogs -- run one workgroup per chain (layout 2, shorter leapfrog) on a
-    // second queue while the rest run one workgroup per site (layout 1, more chains per CU).
-    // The launch ends with its slowest chain; this takes that chain at the faster tick.
-    NutsArgs a2;
-    int wpc2 = 0, dp2 = 0, nv2 = 0, n_lead = 0;
-    if (!use_queue && o.layout == 0 && (layout == 1 || layout == 5 || layout == 7) && a.order && c->split_n > 0 && !eps_dev) {
-        n_lead = c->split_n < count ? c->split_n : count - 1;
-        const int cap = c->n_cu / (2 * o.chains);          // at most half of the CUs for the lead sites
-        if (n_lead > cap) n_lead = cap;
-        if (n_lead > 0) {
-            epx_sampler_opts o2 = o;
-            o2.layout = 2;
-            int layout2;
-            if (build_nuts_args(c, k0, n_lead, o2, a2, &wpc2, &dp2, &nv2, &layout2, count)) return -1;
-            if (layout2 != 2) n_lead = 0;
-            else {
-                a2.seeds = c->seeds_d; a2.draws = c->draws; a2.last = c->last; a2.chain_stats = c->chain_stats;
-                a2.eps_in = nullptr; a2.inv_e_in = nullptr; a2.t_offset = t_offset;
-                a2.carry_eps = a.carry_eps; a2.carry_metric = a.carry_metric;
-                a2.order = a.order;
-                a2.trace = a.trace; a2.trace_sites = a.trace_sites;      // (records are keyed by the REAL site, through `order`, in both launches)
-                a.order = a.order + n_lead;
-            }
-        }
-    }
+    // 5. bind
+    const auto bind = [&](const SamplerPlan &pl) {
+        NutsArgs b = bind_sampler(*c, k0, pl);
+        b.seeds = c->seeds_d; b.draws = c->draws; b.last = c->last; b.chain_stats = c->chain_stats;
+        b.team_passes = c->team_passes;
+        b.eps_in = eps_dev; b.inv_e_in = inv_e_dev; b.t_offset = t_offset;
+        if ((o.reserved & 2) && !eps_dev) { b.carry_eps = c->carry_eps; b.carry_metric = c->carry_metric; }
+        b.order = order;
+        if (ts) { b.trace = c->trace; b.trace_sites = ts; }     // (records are keyed by the REAL site, through `order`, in both launches of a split)
+        return b;
+    };
+    NutsArgs a = bind(p), a2;
+    if (n_lead > 0) { a2 = bind(lead); a.order += n_lead; }
     c->last_split = n_lead;
-#ifdef EPX_STAMPS
-    n_lead = 0; a.order = (c->order_d && c->order_n == count && k0 == 0) ? c->order_d : nullptr; c->last_split = 0;
-    {
-        const int nblk = use_queue ? a.seg_nwg : count * ((o.chains + a.cpb - 1) / a.cpb);      // (a pieced launch: one workgroup per piece)
-        // (two records of 8 sums per workgroup: the roles' shares, then the phases of the row team's pass)
-        // (behind the three records of every workgroup: two records of the first diagnostic form, then six of histograms)
-        if (c->stamps_n < (size_t)3 * nblk + 8) {
-            if (c->stamps) (void)hipFree(c->stamps);
-            HIPCHK(dalloc(&c->stamps, (size_t)(3 * nblk + 8) * 8));
-            c->stamps_n = 3 * nblk + 8;
-        }
-        HIPCHK(hipMemset(c->stamps, 0, (size_t)(3 * nblk + 8) * 64));
-        a.stamps = c->stamps; a.stamps_nrec = nblk;
-        c->stamps_last = 3 * nblk + 8;
+    HIPCHK(hipMemsetAsync(c->team_passes + k0, 0, (size_t)count * 8, c->stream));
+    if (ts) {
+        HIPCHK(hipMemsetAsync(c->trace, 0, trace_elems * 8, c->stream));
+        c->trace_chains = o.chains; c->trace_iter = o.iter; c->trace_last_sites = ts;
     }
+    if (q.on && bind_queue(c, q, count, o, env, p.nv, &a)) return -1;
+#ifdef EPX_STAMPS
+    HIPCHK(hipMemset(c->stamps, 0, stamp_recs * 64));
+    a.stamps = c->stamps; a.stamps_nrec = nblk;
+    c->stamps_last = stamp_recs;
 #endif
+    // 6. launch
     HIPCHK(hipMemcpyAsync(c->seeds_d, seeds, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     int rc = 0;
     if (n_lead > 0) {
         HIPCHK(hipEventRecord(c->ev_fork, c->stream));
         HIPCHK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-        rc = launch_sampler(a2, n_lead, wpc2, dp2, nv2, 2, c->stream2);
+        rc = launch_sampler(lead, a2, n_lead, c->stream2);
         HIPCHK(hipEventRecord(c->ev_join, c->stream2));
     }
-    if (rc == 0) rc = launch_sampler(a, count - n_lead, wpc, dp, nv, layout, c->stream);
+    if (rc == 0) rc = launch_sampler(p, a, count - n_lead, c->stream);
     if (n_lead > 0) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
     if (rc != 0) return fail("NUTS kernel launch failed (%d: %s)", rc, rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported shape");
     HIPCHK(hipEventRecord(c->ev1, c->stream));
+    // 7. epilogue: site statistics, carry history, the hand-off error flag, the hook's records, the time
     RhatArgs ra;
     ra.k0 = k0; ra.chains = o.chains; ra.nkeep = nkeep; ra.P = c->P;
     ra.site_g0 = c->site_g0_d; ra.d = c->d; ra.pg = c->pg;
     ra.draws = c->draws; ra.chain_stats = c->chain_stats; ra.site_stats = c->site_stats;
     hipLaunchKernelGGL(k_site_stats, dim3(count), dim3(128), 0, c->stream, ra);
     HIPCHK(hipGetLastError());
-    if (!eps_dev && !a.dbg) {
+    if (!eps_dev) {
         // history for `adapt = carry` (cheap: one pass over the kept draws); written after every real sampling call
         CarryArgs ca;
         ca.k0 = k0; ca.chains = o.chains; ca.nkeep = nkeep; ca.P = c->P;
@@ -862,22 +833,22 @@ static int run_sampler(epx_ctx *c, int k0, int count, const int64_t *seeds, cons
         c->carry_chains = o.chains;
     }
     c->has_last = 1;
-    c->last_layout = layout;
+    c->last_layout = p.layout;
     c->nsamp = o.chains * nkeep;
     int herr = 0;
     {
         // (no return between a queued copy into this frame and the synchronisation)
         hipError_t e = hipSuccess;
-        if (layout == 5 || layout == 6 || layout == 7 || use_queue) e = hipMemcpyAsync(&herr, c->err_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+        if (duo_layout(p.layout) || q.on) e = hipMemcpyAsync(&herr, c->err_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream);
         const hipError_t es = hipStreamSynchronize(c->stream);
         HIPCHK(e);
         HIPCHK(es);
     }
     if (hook && c->hook_out && !herr) {
-        const size_t rec = (size_t)(4 * nv + 1) * 64;
+        const size_t rec = piece_record_doubles(p.nv);
         for (int k = 0; k < count; ++k)
             HIPCHK(hipMemcpy(c->hook_out + (size_t)k * o.chains * rec,
-                             c->ckpt + (((size_t)k * nb_site + c->hook_t0 + 1) * o.chains) * rec, (size_t)o.chains * rec * 8, hipMemcpyDeviceToHost));
+                             c->ckpt + (((size_t)k * q.nb_site + c->hook_t0 + 1) * o.chains) * rec, (size_t)o.chains * rec * 8, hipMemcpyDeviceToHost));
     }
     if (herr) {
         HIPCHK(hipMemset(c->err_flag, 0, sizeof(int)));
@@ -898,7 +869,7 @@ static int launch_moments(epx_ctx *c, int k0, int count, const double *draws, lo
     MomentArgs a;
     a.k0 = k0; a.d = c->d; a.ld = ld_of(c->d); a.S = S; a.prec_estim = prec_estim;
     size_t lds;
-    if (dense_ws(c, c->d, count, &a.ws, &lds)) return -1;
+    if (dense_ws(c->dense_ws, c->d, count, &a.ws, &lds)) return -1;
     a.draws = draws; a.draws_site0 = site0; a.stride_site = stride_site; a.stride_s = stride_s; a.stride_i = stride_i;
     a.Q = c->Q; a.r = c->r; a.dQi = c->dQi; a.dri = c->dri;
     a.tilt_mean = c->tilt_mean; a.tilt_scatter = c->tilt_scatter; a.flags = c->flags;
@@ -953,11 +924,7 @@ int epx_moments_batch(epx_ctx *c, int k0, int count, const double *samples, int 
     CTX(c);
     if (check_range(c, k0, count)) return -1;
     const size_t need = (size_t)count * S * c->d;
-    if (c->inj_elems < need) {
-        if (c->inj) (void)hipFree(c->inj);
-        HIPCHK(dalloc(&c->inj, need));
-        c->inj_elems = need;
-    }
+    HIPCHK(c->inj.grow(need));
     HIPCHK(hipMemcpy(c->inj, samples, need * 8, hipMemcpyHostToDevice));
     // (S, d) F-order per site: element (s, i) at i*S + s
     if (launch_moments(c, k0, count, c->inj, 0, (long)S * c->d, 1, S, S, prec_estim)) return -1;
@@ -1011,14 +978,12 @@ int epx_nuts_transitions(epx_ctx *c, int k0, int count, const int64_t *seeds, in
     const size_t P = c->P, nc = (size_t)count * chains;
     HIPCHK(hipMemcpy(c->last + (size_t)k0 * chains * P, q0, nc * P * 8, hipMemcpyHostToDevice));
     c->has_last = 1;
-    double *eps_d, *inv_d;
-    HIPCHK(dalloc(&eps_d, nc));
-    HIPCHK(dalloc(&inv_d, nc * P));
+    DevBuf<double> eps_d, inv_d;
+    HIPCHK(eps_d.alloc(nc));
+    HIPCHK(inv_d.alloc(nc * P));
     HIPCHK(hipMemcpy(eps_d, eps, nc * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(inv_d, inv_e, nc * P * 8, hipMemcpyHostToDevice));
-    int rc = run_sampler(c, k0, count, seeds, on, nullptr, eps_d, inv_d, t_offset);
-    (void)hipFree(eps_d); (void)hipFree(inv_d);
-    if (rc) return rc;
+    if (run_sampler(c, k0, count, seeds, on, nullptr, eps_d, inv_d, t_offset)) return -1;
     if (q_out) HIPCHK(hipMemcpy(q_out, c->draws + (size_t)k0 * chains * nt * P, nc * nt * P * 8, hipMemcpyDeviceToHost));
     if (chain_stats) HIPCHK(hipMemcpy(chain_stats, c->chain_stats + (size_t)k0 * chains * ST_COUNT,
                                       nc * ST_COUNT * 8, hipMemcpyDeviceToHost));
@@ -1044,7 +1009,7 @@ int epx_set_site_order(epx_ctx *c, const int32_t *order, int count) {
         if (order[i] < 0 || order[i] >= count || seen[order[i]]) return fail("site order is not a permutation of 0..%d", count - 1);
         seen[order[i]] = 1;
     }
-    if (!c->order_d) HIPCHK(dalloc(&c->order_d, (size_t)c->K));
+    HIPCHK(c->order_d.grow((size_t)c->K));
     HIPCHK(hipMemcpy(c->order_d, order, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
     c->order_n = count;
     return 0;
@@ -1053,15 +1018,13 @@ int epx_set_site_order(epx_ctx *c, const int32_t *order, int count) {
 int epx_set_piece_queue(epx_ctx *c, int piece_len, const double *rate) {
     CTX(c);
     if (piece_len <= 0) { c->dyn_len = 0; return 0; }
-    if (!c->dyn_words) HIPCHK(dalloc(&c->dyn_words, 2 * (size_t)c->K));
+    HIPCHK(c->dyn_words.grow(2 * (size_t)c->K));
     c->dyn_has_rate = rate != nullptr;
     if (rate) {
         for (int k = 0; k < c->K; ++k)
             if (!(rate[k] > 0.0) || !std::isfinite(rate[k])) return fail("predicted work of site %d is not positive", k);
-        if (!c->dyn_rate) HIPCHK(dalloc(&c->dyn_rate, (size_t)c->K));
+        HIPCHK(c->dyn_rate.grow((size_t)c->K));
         HIPCHK(hipMemcpy(c->dyn_rate, rate, (size_t)c->K * 8, hipMemcpyHostToDevice));
-        if (!c->dyn_rate_h) c->dyn_rate_h = new std::vector<double>();
-        c->dyn_rate_h->assign(rate, rate + c->K);
     }
     c->dyn_len = piece_len;
     return 0;
@@ -1150,18 +1113,19 @@ int epx_logdensity_grad_layout(epx_ctx *c, int k, const double *theta, int layou
     epx_sampler_opts o;
     memset(&o, 0, sizeof o);
     o.chains = 1; o.iter = 2; o.warmup = 1; o.thin = 1; o.init = EPX_INIT_PREV; o.max_depth = 10; o.layout = layout_req;
-    NutsArgs a;
-    int wpc, dp, nv, layout;
-    if (build_nuts_args(c, k, 1, o, a, &wpc, &dp, &nv, &layout)) return -1;
+    SamplerPlan p;
+    if (plan_sampler(*c, 1, o, sampler_env(), &p)) return -1;
+    HIPCHK(c->stack.grow(p.a.stack_stride));           // (one site, one chain)
+    NutsArgs a = bind_sampler(*c, k, p);
     const size_t P = c->P;
     HIPCHK(hipMemcpy(c->dbg + P + 1, theta, P * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(c->dbg_seed, 0, sizeof(int64_t)));
     a.seeds = c->dbg_seed;
     a.last = c->dbg + P + 1 - (size_t)k * P;      // kernel reads last[(k*chains + chain)*P], chains = 1
     a.dbg = c->dbg;
-    int rc = launch_sampler(a, 1, wpc, dp, nv, layout, c->stream);
+    int rc = launch_sampler(p, a, 1, c->stream);
     if (rc != 0) return fail("NUTS kernel launch failed (%d)", rc);
-    c->last_layout = layout;
+    c->last_layout = p.layout;
     HIPCHK(hipStreamSynchronize(c->stream));
     std::vector<double> outv(P + 1);
     HIPCHK(hipMemcpy(outv.data(), c->dbg, (P + 1) * 8, hipMemcpyDeviceToHost));
@@ -1214,7 +1178,7 @@ static int launch_global(epx_ctx *c, const double *packed_dev, double df, int wa
     a.tgt = tgt; a.crit = crit;
     a.d = c->d; a.ld = ld_of(c->d); a.want_moments = want_moments;
     size_t lds;
-    if (dense_ws(c, c->d, c->K, &a.ws, &lds)) return -1;
+    if (dense_ws(c->dense_ws, c->d, c->K, &a.ws, &lds)) return -1;
     a.packed = packed_dev; a.Q0 = c->Q0; a.r0 = c->r0; a.df = df;
     a.Q = c->Q; a.r = c->r; a.S = c->S; a.m = c->m; a.flag = c->iflags;
     if (set_lds(k_global, lds)) return -1;
@@ -1320,12 +1284,7 @@ int epx_damp_sweep(epx_ctx *c, int ndf, const double *dfs, const double *packed_
     if (ndf < 1 || !dfs || !m_target || !S_target || !out) return fail("damp sweep: missing argument");
     const size_t d = c->d, d2 = d * d, ntgt = 2 * (d + d2) + 2;
     const size_t need = ntgt + (size_t)ndf * 5;
-    if (c->sweep_elems < need) {
-        if (c->sweep_buf) (void)hipFree(c->sweep_buf);
-        c->sweep_buf = nullptr; c->sweep_elems = 0;
-        HIPCHK(dalloc(&c->sweep_buf, need));
-        c->sweep_elems = need;
-    }
+    HIPCHK(c->sweep_buf.grow(need));
     std::vector<double> h(ntgt, 0.0);
     memcpy(h.data(), m_target, d * 8);
     memcpy(h.data() + d, S_target, d2 * 8);
@@ -1383,7 +1342,7 @@ int epx_force_pd(epx_ctx *c, double df, double thresh, double min_eig_target, ui
     ForceArgs a;
     a.d = c->d; a.ld = ld_of(c->d);
     size_t lds;
-    if (dense_ws(c, c->d, c->K, &a.ws, &lds)) return -1;
+    if (dense_ws(c->dense_ws, c->d, c->K, &a.ws, &lds)) return -1;
     a.Qi = c->Qi; a.dQi = c->dQi; a.df = df; a.thresh = thresh; a.target = min_eig_target;
     a.forced = c->flags; a.min_eig = c->min_eig;
     if (set_lds(k_force_pd, lds)) return -1;
@@ -1395,16 +1354,6 @@ int epx_force_pd(epx_ctx *c, double df, double thresh, double min_eig_target, ui
 }
 
 // ------------------------------------------------------ stand-alone util ops
-static int util_dense_ws(int d, int nb, DenseWs *ws, size_t *lds, double **owned) {
-    *owned = nullptr;
-    const size_t bytes = dense_slot_doubles(d) * 8;
-    if (bytes + 1024 <= LDS_CAP) { ws->use_lds = 1; ws->global = nullptr; *lds = bytes; return 0; }
-    ws->use_lds = 0; *lds = 0;
-    HIPCHK(dalloc(owned, dense_slot_doubles(d) * nb));
-    ws->global = *owned;
-    return 0;
-}
-
 static int need_device(int device) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -1428,13 +1377,14 @@ int epx_invert_normal_params(int device, int d, int nb, double *A, double *b, in
     if (d < 1 || nb < 1) return fail("bad sizes");
     InvertArgs a;
     a.d = d; a.ld = ld_of(d); a.cho_form = cho_form;
-    size_t lds; double *owned;
-    if (util_dense_ws(d, nb, &a.ws, &lds, &owned)) return -1;
-    double *Ad, *bd = nullptr; int32_t *infod;
-    HIPCHK(dalloc(&Ad, (size_t)nb * d * d));
-    HIPCHK(dalloc(&infod, nb));
+    size_t lds;
+    DevBuf<double> ws, Ad, bd;
+    DevBuf<int32_t> infod;
+    if (dense_ws(ws, d, nb, &a.ws, &lds)) return -1;
+    HIPCHK(Ad.alloc((size_t)nb * d * d));
+    HIPCHK(infod.alloc(nb));
     HIPCHK(hipMemcpy(Ad, A, (size_t)nb * d * d * 8, hipMemcpyHostToDevice));
-    if (b) { HIPCHK(dalloc(&bd, (size_t)nb * d)); HIPCHK(hipMemcpy(bd, b, (size_t)nb * d * 8, hipMemcpyHostToDevice)); }
+    if (b) { HIPCHK(bd.alloc((size_t)nb * d)); HIPCHK(hipMemcpy(bd, b, (size_t)nb * d * 8, hipMemcpyHostToDevice)); }
     a.A = Ad; a.b = bd; a.info = infod;
     if (set_lds(k_invert, lds)) return -1;
     hipLaunchKernelGGL(k_invert, dim3(nb), dim3(256), lds, 0, a);
@@ -1443,7 +1393,6 @@ int epx_invert_normal_params(int device, int d, int nb, double *A, double *b, in
     HIPCHK(hipMemcpy(A, Ad, (size_t)nb * d * d * 8, hipMemcpyDeviceToHost));
     if (b) HIPCHK(hipMemcpy(b, bd, (size_t)nb * d * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(info, infod, nb * sizeof(int32_t), hipMemcpyDeviceToHost));
-    (void)hipFree(Ad); (void)hipFree(infod); if (bd) (void)hipFree(bd); if (owned) (void)hipFree(owned);
     return 0;
 }
 
@@ -1453,13 +1402,14 @@ int epx_olse(int device, int d, int nb, double *S, int n, const double *P, int32
     if (d < 1 || nb < 1) return fail("bad sizes");
     OlseArgs a;
     a.d = d; a.ld = ld_of(d); a.n = n;
-    size_t lds; double *owned;
-    if (util_dense_ws(d, nb, &a.ws, &lds, &owned)) return -1;
-    double *Sd, *Pd = nullptr; int32_t *infod;
-    HIPCHK(dalloc(&Sd, (size_t)nb * d * d));
-    HIPCHK(dalloc(&infod, nb));
+    size_t lds;
+    DevBuf<double> ws, Sd, Pd;
+    DevBuf<int32_t> infod;
+    if (dense_ws(ws, d, nb, &a.ws, &lds)) return -1;
+    HIPCHK(Sd.alloc((size_t)nb * d * d));
+    HIPCHK(infod.alloc(nb));
     HIPCHK(hipMemcpy(Sd, S, (size_t)nb * d * d * 8, hipMemcpyHostToDevice));
-    if (P) { HIPCHK(dalloc(&Pd, (size_t)nb * d * d)); HIPCHK(hipMemcpy(Pd, P, (size_t)nb * d * d * 8, hipMemcpyHostToDevice)); }
+    if (P) { HIPCHK(Pd.alloc((size_t)nb * d * d)); HIPCHK(hipMemcpy(Pd, P, (size_t)nb * d * d * 8, hipMemcpyHostToDevice)); }
     a.S = Sd; a.P = Pd; a.info = infod;
     if (set_lds(k_olse, lds)) return -1;
     hipLaunchKernelGGL(k_olse, dim3(nb), dim3(256), lds, 0, a);
@@ -1467,7 +1417,6 @@ int epx_olse(int device, int d, int nb, double *S, int n, const double *P, int32
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(S, Sd, (size_t)nb * d * d * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(info, infod, nb * sizeof(int32_t), hipMemcpyDeviceToHost));
-    (void)hipFree(Sd); (void)hipFree(infod); if (Pd) (void)hipFree(Pd); if (owned) (void)hipFree(owned);
     return 0;
 }
 
@@ -1475,12 +1424,11 @@ int epx_rng_probe(int device, uint64_t seed, int chain, uint32_t t, uint32_t kin
                   double *out4) {
     DeviceGuard guard;
     if (need_device(device)) return -1;
-    double *od;
-    HIPCHK(dalloc(&od, 4));
+    DevBuf<double> od;
+    HIPCHK(od.alloc(4));
     hipLaunchKernelGGL(k_rng_probe, dim3(1), dim3(64), 0, 0, seed, chain, t, kind, a, b, od);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out4, od, 32, hipMemcpyDeviceToHost));
-    (void)hipFree(od);
     return 0;
 }

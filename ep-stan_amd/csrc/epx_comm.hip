@@ -58,15 +58,6 @@ int load_rccl() {
         if (r_ != ncclSuccess) return fail("%s failed: %s (%s:%d)", #x, g_rccl.GetErrorString(r_), __FILE__, __LINE__); \
     } while (0)
 
-int stage(epx_ctx *c, size_t n) {
-    if (c->comm_stage_n >= n) return 0;
-    if (c->comm_stage) (void)hipFree(c->comm_stage);
-    c->comm_stage = nullptr; c->comm_stage_n = 0;
-    HIPCHK(dalloc(&c->comm_stage, n));
-    c->comm_stage_n = n;
-    return 0;
-}
-
 }  // namespace
 
 int epx_comm_unique_id(void *id_out) {
@@ -151,7 +142,7 @@ int epx_comm_allreduce(epx_ctx *c, double *buf, int n, int op) {
         return 0;
     }
     if (!c->comm) return 0;                         // one rank: identity
-    if (stage(c, (size_t)n)) return -1;
+    HIPCHK(c->comm_stage.grow((size_t)n));
     const ncclRedOp_t ops[] = {ncclSum, ncclMin, ncclMax};
     HIPCHK(hipMemcpyAsync(c->comm_stage, buf, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     NCCLCHK(g_rccl.AllReduce(c->comm_stage, c->comm_stage, (size_t)n, ncclDouble, ops[op],
@@ -173,7 +164,7 @@ int epx_comm_allgather(epx_ctx *c, const double *in, int n, double *out) {
     }
     if (!c->comm) { memcpy(out, in, (size_t)n * 8); return 0; }
     const size_t tot = (size_t)n * (1 + c->comm_size);
-    if (stage(c, tot)) return -1;
+    HIPCHK(c->comm_stage.grow(tot));
     HIPCHK(hipMemcpyAsync(c->comm_stage, in, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     NCCLCHK(g_rccl.AllGather(c->comm_stage, c->comm_stage + n, (size_t)n, ncclDouble,
                              static_cast<ncclComm_t>(c->comm), c->stream));

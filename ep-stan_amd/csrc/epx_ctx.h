@@ -23,94 +23,132 @@ int epx_fail(const char *fmt, ...);
     if (!(c)) return fail("null context");          \
     HIPCHK(hipSetDevice((c)->device));
 
+// A device array of n elements of T that frees itself: every device allocation of the library is one.  It converts to
+// T * where the array is used.
 template <typename T>
-static hipError_t dalloc(T **p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    return hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T));
-}
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    operator T *() const { return p; }
+
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr; n = 0;
+    }
+    // exactly `want` elements (room for one at least); the old array is freed first
+    hipError_t alloc(size_t want) {
+        release();
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), (want ? want : 1) * sizeof(T));
+        if (e == hipSuccess) n = want;
+        else p = nullptr;
+        return e;
+    }
+    // at least `want` elements: free, then allocate (peak memory: the new array alone)
+    hipError_t grow(size_t want) { return want <= n ? hipSuccess : alloc(want); }
+    // at least `want` elements: allocate first and keep the old array if that fails (the sticky error is cleared)
+    bool try_grow(size_t want) {
+        if (want <= n) return true;
+        T *q = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&q), want * sizeof(T)) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        release();
+        p = q; n = want;
+        return true;
+    }
+};
 
 static const size_t LDS_CAP = 160 * 1024;
 
 struct epx_ctx {
-    int device, model, K, D, d, P;
-    int64_t N;
-    hipStream_t stream;
+    int device = 0, model = 0, K = 0, D = 0, d = 0, P = 0;
+    int64_t N = 0;
+    hipStream_t stream = nullptr;
     std::vector<int64_t> k_lim;
     // multi-group sites (K < J): groups per site, device copies of the prefix sums / row limits
     std::vector<int> g_cnt;
-    int *site_g0_d;
-    int64_t *g_lim_d;
-    int multi, ng_max, nt_max, pg;
-    int n_max;
+    DevBuf<int> site_g0_d;
+    DevBuf<int64_t> g_lim_d;
+    int multi = 0, ng_max = 0, nt_max = 0, pg = 0;
+    int n_max = 0;
     // device buffers
-    int64_t *k_lim_d;
-    double *X;
-    uint8_t *y;
-    int *y32;
-    double *yd;                     // real responses (Gaussian-likelihood family), else NULL
-    int gauss;
-    double *Q0, *r0, *Q, *r, *S, *m;
-    double *Qi, *ri, *Qi2, *ri2, *dQi, *dri;
-    double *cav_Om, *cav_mu;
-    double *tilt_mean, *tilt_scatter;
-    uint8_t *flags;
-    int *iflags;              // [4]
-    double *packed, *partial; // sums
-    int nslice;
-    double *dense_ws;         // global workspace for dense kernels (lazily sized)
-    size_t dense_ws_slots;
+    DevBuf<int64_t> k_lim_d;
+    DevBuf<double> X;
+    DevBuf<uint8_t> y;
+    DevBuf<int> y32;
+    DevBuf<double> yd;              // real responses (Gaussian-likelihood family), else NULL
+    int gauss = 0;
+    DevBuf<double> Q0, r0, Q, r, S, m;
+    DevBuf<double> Qi, ri, Qi2, ri2, dQi, dri;
+    DevBuf<double> cav_Om, cav_mu;
+    DevBuf<double> tilt_mean, tilt_scatter;
+    DevBuf<uint8_t> flags;
+    DevBuf<int> iflags;             // [4]
+    DevBuf<double> packed, partial; // sums
+    int nslice = 0;
+    DevBuf<double> dense_ws;        // global workspace for dense kernels (lazily sized)
     // sampler buffers (lazily sized)
-    int s_chains, s_nkeep;
-    double *draws, *last, *chain_stats, *site_stats, *stack;
-    double *team_passes;            // K: row-team passes of the last sampling call per site (layout 7; 0 elsewhere)
-    size_t stack_elems;
-    int64_t *seeds_d;
-    double *dbg;              // [1+P] lp, grad ; [P] theta (test hook)
-    int64_t *dbg_seed;
-    double *inj;              // injected samples (test hook)
-    size_t inj_elems;
-    int has_last;
-    int nsamp;                // draws per site of the last tilted/moments call
-    double last_df;
-    hipEvent_t ev0, ev1;
-    hipStream_t stream2;            // second queue of a split sampling launch (epx_set_site_split)
-    hipEvent_t ev_fork, ev_join;
-    int split_n, last_split, n_cu;
-    unsigned long long *stamps;
-    size_t stamps_n, stamps_last;
-    int last_layout;
-    int *order_d;
-    int order_n;
-    int last_segments;
-    double *ckpt;
-    size_t ckpt_n;
+    int s_chains = 0, s_nkeep = 0;
+    DevBuf<double> draws, last, chain_stats, site_stats, stack;
+    DevBuf<double> team_passes;     // K: row-team passes of the last sampling call per site (layout 7; 0 elsewhere)
+    DevBuf<int64_t> seeds_d;
+    DevBuf<double> dbg;             // [1+P] lp, grad ; [P] theta (test hook)
+    DevBuf<int64_t> dbg_seed;
+    DevBuf<double> inj;             // injected samples (test hook)
+    int has_last = 0;
+    int nsamp = 0;                  // draws per site of the last tilted/moments call
+    double last_df = 0.0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipStream_t stream2 = nullptr;  // second queue of a split sampling launch (epx_set_site_split)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int split_n = 0, last_split = 0, n_cu = 0;
+    DevBuf<unsigned long long> stamps;  // diagnostic build: records of 8 cycle sums ...
+    size_t stamps_last = 0;             // ... and how many the last sampling call wrote
+    int last_layout = 0;
+    DevBuf<int> order_d;
+    int order_n = 0;
+    int last_segments = 0;
+    DevBuf<double> ckpt;
     // piece queue (epx_set_piece_queue): transitions per claim (0: off), predicted work per transition of the sites
-    int dyn_len, dyn_has_rate;
-    int *dyn_lens_d;          // per-site piece lengths of the queue (device), their host copy below
-    std::vector<double> *dyn_rate_h;
-    double *dyn_rate;
-    int *dyn_words;           // [progress (K) | busy (K)]
-    double *sweep_buf;        // damping sweep: target block + ndf x 5 criteria
-    size_t sweep_elems;
-    double *carry_eps, *carry_metric;   // adapt = carry: K x chains step sizes, K x P diagonal metrics (lazily sized)
-    int carry_chains;                   // chains the history was recorded with (0: none)
-    double *min_eig;          // force-pd fallback: smallest eigenvalue per site (K)
+    int dyn_len = 0, dyn_has_rate = 0;
+    DevBuf<double> dyn_rate;
+    DevBuf<int> dyn_words;          // [progress (K) | busy (K)]
+    DevBuf<double> sweep_buf;       // damping sweep: target block + ndf x 5 criteria
+    DevBuf<double> carry_eps, carry_metric;   // adapt = carry: K x chains step sizes, K x P diagonal metrics (lazily sized)
+    int carry_chains = 0;                     // chains the history was recorded with (0: none)
+    DevBuf<double> min_eig;         // force-pd fallback: smallest eigenvalue per site (K)
     // in-library RCCL binding (epx_comm.hip); comm == nullptr: single rank
-    void *comm;               // ncclComm_t
-    int comm_rank, comm_size;
-    int (*comm_ext)(double *, long long, int, void *);   // host transport given by the caller (epx_comm_init_host) ...
-    void *comm_ext_user;                                 // ... used instead of RCCL when set
-    double *comm_stage;       // device staging of the small host-side collectives
-    size_t comm_stage_n;
-    int *err_flag;            // device word the sampler kernels set when a hand-off spin gives up
+    void *comm = nullptr;           // ncclComm_t
+    int comm_rank = 0, comm_size = 0;
+    int (*comm_ext)(double *, long long, int, void *) = nullptr;   // host transport given by the caller (epx_comm_init_host) ...
+    void *comm_ext_user = nullptr;                                 // ... used instead of RCCL when set
+    DevBuf<double> comm_stage;      // device staging of the small host-side collectives
+    DevBuf<int> err_flag;           // device word the sampler kernels set when a hand-off spin gives up
     // epx_sample_piece (test hook): one piece of ONE transition from injected checkpoint records
-    int hook_t0;              // > 0 while such a call runs
-    const double *hook_in;    // host: K x chains records (csrc/epx_pieces.h layout)
-    double *hook_out;         // host: the records the piece leaves at boundary hook_t0 + 1
+    int hook_t0 = 0;                    // > 0 while such a call runs
+    const double *hook_in = nullptr;    // host: K x chains records (csrc/epx_pieces.h layout)
+    double *hook_out = nullptr;         // host: the records the piece leaves at boundary hook_t0 + 1
     // per-transition trace of the sampler (epx_set_trace, test hook): the first trace_sites sites of a sampling call
-    int trace_sites, trace_chains, trace_iter, trace_last_sites;     // (trace_last_sites: what the last sampling call recorded)
-    double *trace;
-    size_t trace_n;
+    int trace_sites = 0, trace_chains = 0, trace_iter = 0, trace_last_sites = 0;     // (trace_last_sites: what the last sampling call recorded)
+    DevBuf<double> trace;
+
+    epx_ctx() = default;
+    epx_ctx(const epx_ctx &) = delete;
+    epx_ctx &operator=(const epx_ctx &) = delete;
+    // (the device arrays free themselves behind this, as members; the caller has made the context's device current)
+    ~epx_ctx() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_join) (void)hipEventDestroy(ev_join);
+        if (stream2) (void)hipStreamDestroy(stream2);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 

@@ -197,7 +197,7 @@ struct NutsArgs {
     int *dyn_prog, *dyn_busy;
     const double *dyn_rate;       // predicted work per transition of every site of the batch, or NULL (all equal)
     int dyn_len, dyn_count;
-    const int *dyn_lens;          // per site: transitions of one of ITS pieces (pieces of equal predicted work), or NULL: dyn_len for all
+    const int *dyn_lens;          // per site: transitions of one of ITS pieces, or NULL (what the host gives): dyn_len for all
     int dyn_nb;                   // checkpoint records (piece boundaries) reserved per site
     int dyn_tail_div;             // the pieces behind 3/4 of a site's run are 1/dyn_tail_div of the nominal length (epx_pieces.h)
     int dyn_hook;                 // epx_sample_piece: a site is released as FINISHED behind its one transition (never claimable twice)

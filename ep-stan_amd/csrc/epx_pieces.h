@@ -69,11 +69,11 @@ __host__ __device__ constexpr size_t piece_record_doubles(int nv) { return (size
 // for the first three quarters of the run, a quarter of it (at least 1) behind transition T1 = the last multiple of L at or
 // below 3/4 of the run.  A pieced launch ends with the LAST piece of every workgroup, so on average half a piece of every
 // CU is idle at the end (at C5 a nominal piece is ~1 s of a 31 s launch): the short pieces are handed out when the queue
-// runs dry, and the claim by largest remaining work then evens the workgroups out four times finer.  (Nominal lengths are
-// per site when the host gives them -- NutsArgs::dyn_lens -- else one for all.)
+// runs dry, and the claim by largest remaining work then evens the workgroups out four times finer.  (The host gives one
+// nominal length for all sites, dyn_len; NutsArgs::dyn_lens, per-site lengths, stays NULL.)
 template <class Args>
 __device__ __forceinline__ int piece_len_of(Args &a, int site) { return a.dyn_lens ? a.dyn_lens[site] : a.dyn_len; }
-// (div: NutsArgs::dyn_tail_div -- 4 by default; 1 = one length throughout, the form of rounds 2-4: EPX_PIECE_TAIL_DIV for A/B)
+// (div: NutsArgs::dyn_tail_div -- 4 for the streaming sampler, 1 = one length throughout for the resident layouts: plan_queue)
 __host__ __device__ inline int piece_short_len(int len, int div) { return len >= div ? len / div : 1; }
 __host__ __device__ inline int piece_switch_at(int iter, int len) { return (iter - iter / 4) / len * len; }       // T1
 __host__ __device__ inline int piece_boundaries(int iter, int len, int div) {        // boundaries behind the start: pieces of a site
