@@ -2,7 +2,13 @@
 """Headline benchmark: site-updates/sec (and EP iters/sec) of the EP inner loop on synthetic
 hierarchical logistic regression, model m4b, chains=4, iter=200 (S=400 draws per site update).
 
-    python bench.py --gpus N --steps K --warmup W [--config c3|c2|c5shard]
+    python bench.py --gpus N --steps K --warmup W [--config c3|c2|c5shard] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the dump if asked for, the
+line.  Everything else the benchmark measures or checks takes runs of its own and sits behind --full: the parity EP
+iteration behind the timed region with the CPU port's re-run of its first sites (`cpu_baseline`, `parity`) and the
+`secondary` records of the other two single-GPU configurations (C2, one C5 shard).  --cpu-sites, --parity-sites,
+--cpu-seq-sites, --cpu-threads and --no-secondary shape those parts of a --full run.
 
 Default workload = BASELINE.json configs[2], the largest single-GPU configuration: 512 sites per
 GPU, D=32, n_j=500 (N=1 is C3; N=8 is exactly C4: J=4096 sharded over 8 GPUs, weak scaling).
@@ -45,7 +51,7 @@ CONFIGS = {
     # name: (sites per GPU, D, n_j, correlated covariates, default steps, default warm-up)
     'c2': (64, 16, 200, 1, 20, 5),
     'c3': (512, 32, 500, 1, 20, 5),      # the driver's command: --steps 20 --warmup 5
-    'c5shard': (512, 128, 2000, 0, 2, 2),      # (the secondary record of the default run uses these too: README's number = the driver's)
+    'c5shard': (512, 128, 2000, 0, 2, 2),      # (the secondary record of a --full run uses these too: README's number = the driver's)
 }
 
 
@@ -766,12 +772,18 @@ def main():
     ap.add_argument('--adapt', default='fresh', choices=['fresh', 'carry'],
                     help="'fresh' = the reference's behaviour (default, the headline); 'carry' = opt-in carried adaptation")
     ap.add_argument('--cor-input', type=int, default=None, help='0: uncorrelated covariates (fit.py cor_input=False)')
-    ap.add_argument('--cpu-sites', type=int, default=None, help='sites of the all-cores cpu_baseline leg (fast build); 0 disables it; default: two per thread the process can really run (affinity capped by the cgroup quota), at most 64')
+    ap.add_argument('--full', action='store_true',
+                    help='behind the timed steps, also run everything else the benchmark measures or checks: the parity EP '
+                         'iteration with the CPU port\'s re-run of its first sites (cpu_baseline, parity) and the secondary '
+                         'records (C2, one C5 shard).  Off by default: a plain run sets up, warms up, times its steps, '
+                         'writes --dump-outputs and prints the line')
+    ap.add_argument('--cpu-sites', type=int, default=None, help='--full only: sites of the all-cores cpu_baseline leg (fast build); 0 disables it; default: two per thread the process can really run (affinity capped by the cgroup quota), at most 64')
     ap.add_argument('--parity-sites', type=int, default=None, help='sites the strict build re-does for the parity record (default: --cpu-sites, at most 32)')
     ap.add_argument('--cpu-seq-sites', type=int, default=3, help='sites of the reference-faithful schedule')
     ap.add_argument('--cpu-threads', type=int, default=0)
     ap.add_argument('--no-secondary', dest='secondary', action='store_false',
-                    help='skip the C2 / C5-shard records behind the headline (default: measured when the headline is C3 on one GPU)')
+                    help='--full only: skip the C2 / C5-shard records behind the headline (a --full run measures them when the '
+                         'headline is C3 on one GPU)')
     ap.add_argument('--dry-run', action='store_true',
                     help='launch + rendezvous only (no GPU work): checks that --gpus N starts N ranks')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -789,15 +801,23 @@ def main():
     warm = args.warmup if args.warmup is not None else warm
 
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')      # before anything touches the GPU (see spawn_ranks)
-    # the CPU legs are sized by what the host really gives this process (they are a bounded sample, and the default run has
-    # to stay within minutes): two sites per usable thread's worth of chains, i.e. 8 (site, chain) work items per thread ->
-    # 32 sites on this pool's GPU boxes (256 hardware threads, cgroup quota 16 CPUs), handed out dynamically
-    limits = host_cpu_limits()
-    width = cpu_width(limits, args.cpu_threads)[0]
-    if args.cpu_sites is None:
-        args.cpu_sites = int(min(64, max(4, 2 * width)))
-    if args.parity_sites is None:
-        args.parity_sites = int(min(32, max(2, args.cpu_sites))) if args.cpu_sites > 0 else 0
+    limits = None
+    if args.full:
+        # the CPU legs are sized by what the host really gives this process (they are a bounded sample, and a --full run
+        # has to stay within minutes): two sites per usable thread's worth of chains, i.e. 8 (site, chain) work items per
+        # thread -> 32 sites on a host of 256 hardware threads under a cgroup quota of 16 CPUs, handed out dynamically
+        limits = host_cpu_limits()
+        width = cpu_width(limits, args.cpu_threads)[0]
+        if args.cpu_sites is None:
+            args.cpu_sites = int(min(64, max(4, 2 * width)))
+        if args.parity_sites is None:
+            args.parity_sites = int(min(32, max(2, args.cpu_sites))) if args.cpu_sites > 0 else 0
+    else:
+        # a plain run: nothing behind the timed steps but the dump and the line.  Asking for a CPU leg without --full is a
+        # mistake worth a message, not something to drop silently
+        if (args.cpu_sites or 0) > 0 or (args.parity_sites or 0) > 0:
+            ap.error('--cpu-sites / --parity-sites above 0 need --full: the parity iteration and the CPU leg run only there')
+        args.cpu_sites, args.parity_sites, args.secondary = 0, 0, False
     if args.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
 
@@ -839,7 +859,9 @@ def main():
     sizes = (sites, D, n, cor, steps, warm)
     out, M = measure(args, args.config, sizes, comm, rank, world, local_rank, on_gpu,
                      custom=(args.sites, args.D, args.n) != (None, None, None), dump=args.dump_outputs)
-    # ---- behind the timed region.  ORDER MATTERS: the parity iteration is an EP iteration, i.e. it
+    if out is not None:
+        out['full'] = bool(args.full)        # False: the line of a plain run, without cpu_baseline / parity / secondary
+    # ---- behind the timed region (--full only; a plain run falls through to its line).  ORDER MATTERS: the parity iteration is an EP iteration, i.e. it
     # contains the all-reduces of epx_update_trial, so EVERY rank runs it; only behind it do ranks != 0 leave, and from
     # there on rank 0 calls nothing collective (cpu_leg: engine getters, device-local test hooks, the CPU oracle).
     # A watchdog guarantees the headline line whatever happens to this part: if the parity iteration or the CPU leg has

@@ -19,11 +19,12 @@ for w in $WHICH; do
   rm -rf $OUT/${w}_*
   case $w in
   c2)
-    python3 $REPO/bench.py --config c2 > $OUT/c2_bench.json 2> $OUT/c2_bench.err
+    python3 $REPO/bench.py --config c2 --full > $OUT/c2_bench.json 2> $OUT/c2_bench.err
     prof c2 --config c2 --steps 3 --warmup 1 ;;
   c3)
-    # the driver's command, for the bench line AND for every profiling pass: the same launches are timed and counted
-    python3 $REPO/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/c3_bench.json 2> $OUT/c3_bench.err
+    # the driver's command, for the bench line (--full: with cpu_baseline, parity and the secondary records behind the
+    # timed steps) AND for every profiling pass: the same launches are timed and counted
+    python3 $REPO/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/c3_bench.json 2> $OUT/c3_bench.err
     prof c3 --gpus 1 --steps 20 --warmup 5
     # instruction mix of the sampler over the same command (SQ counters, two passes of at most 8)
     rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_VALU_MFMA_MOPS_F64 --kernel-trace -d $OUT/c3_mix_a -o run -- python3 $REPO/bench.py --gpus 1 --steps 20 --warmup 5 --cpu-sites 0 --no-secondary > $OUT/c3_mix_a.log 2>&1

@@ -185,15 +185,16 @@ def _bench_line(res):
 @pytest.mark.parametrize('world', [2, 8])
 def test_bench_runs_end_to_end_on_cpu_with_the_parity_and_cpu_legs(world):
     """`bench.py --gpus N` as the driver launches it (torch.distributed.run, one process per rank), with the oracle
-    engine and a gloo transport in place of the device, at its DEFAULT form: the parity EP iteration and the CPU leg
+    engine and a gloo transport in place of the device, in its --full form: the parity EP iteration and the CPU leg
     behind the timed region are ON.  The parity iteration is collective (the all-reduces of the update phase), so every
     rank has to stay for it; only behind it may ranks != 0 leave.  (Round 5 shipped the opposite order: rank 0 ran the
     collective alone, 'Connection closed by peer' over gloo, a hang over RCCL -- and this test passed --cpu-sites 0.)
     ONE JSON line from rank 0 with the whole-job value, cpu_baseline and parity filled in, clean exit of every rank."""
     res = _run_torchrun(world, os.path.join(ROOT, 'tests', 'bench_cpu_smoke.py'),
                         ['--gpus', str(world), '--sites', '2', '--D', '3', '--rows', '30', '--siter', '20', '--steps', '2',
-                         '--warmup', '1', '--cpu-sites', '2'])
+                         '--warmup', '1', '--full', '--cpu-sites', '2'])
     out = _bench_line(res)
+    assert out['full'] is True
     assert 'Connection closed' not in res.stderr and 'Traceback' not in res.stderr, res.stderr[-3000:]
     assert out['n_gpus'] == world and out['steps'] == 2 and out['warmup'] == 1 and out['scaling'] == 'weak'
     assert out['config']['rccl_world_size'] == world
@@ -218,6 +219,21 @@ def test_bench_without_the_cpu_leg_at_world_size_8_on_cpu():
     out = _bench_line(res)
     assert out['n_gpus'] == 8 and 'cpu_baseline' not in out
     np.testing.assert_allclose(out['value'], 16 * 2 / (out['ms_per_step'] * 1e-3 * 2), rtol=1e-9)
+
+
+def test_plain_bench_run_stops_behind_its_timed_steps_on_cpu():
+    """Without --full: no parity iteration, no CPU leg, no secondary records -- the line carries the headline keys and says
+    that it is a plain run's; the same command with --cpu-sites above 0 is refused with a pointer to --full."""
+    import subprocess
+    common = ['--gpus', '2', '--sites', '2', '--D', '3', '--rows', '30', '--siter', '20', '--steps', '2', '--warmup', '1']
+    out = _bench_line(_run_torchrun(2, os.path.join(ROOT, 'tests', 'bench_cpu_smoke.py'), common))
+    assert out['full'] is False and not {'cpu_baseline', 'parity', 'secondary'} & set(out)
+    assert out['metric'] == 'site-updates/sec' and out['unit'] == 'site-updates/s' and out['dtype'] == 'f64'
+    assert out['higher_is_better'] is True and out['steps'] == 2 and out['warmup'] == 1
+    np.testing.assert_allclose(out['value'], 4 * 2 / (out['ms_per_step'] * 1e-3 * 2), rtol=1e-9)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-run', '--cpu-sites', '2'],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, text=True)
+    assert res.returncode == 2 and '--full' in res.stderr and not res.stdout.strip()
 
 
 def test_no_rank_leaves_bench_before_the_last_collective():
