@@ -27,23 +27,6 @@
 
 namespace epx {
 
-
-
-// In-kernel cycle stamps exist only in the diagnostic build (-DEPX_STAMPS); its
-// run time is never quoted, only the shares of the segments.
-#ifdef EPX_STAMPS
-#define STAMP(i)                                                                   \
-    do {                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-        unsigned long long t_ = __builtin_amdgcn_s_memtime();                      \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                        \
-        tacc[i] += t_ - tprev; tprev = t_;                                         \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-    } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
-
 template <int NV, int DP, int WPC, bool OML, bool STL, bool GAUSS>
 __global__ void __launch_bounds__(256)
 k_nuts(NutsArgs a) {
@@ -112,7 +95,6 @@ k_nuts(NutsArgs a) {
     // ------------------------------------------------------------- state
     V mu, inv_e, qs, gs, zq, zp, zg, pq, pp, pg, mq, mp, mg, rho, psp, psm;
     V n_rho, n_psl, bq, bg, psr, wmean, wm2;
-    double lps = 0, zlp = 0, plp = 0, mlp = 0, b_key = 0, b_plp = 0;
     FORV {
         const int e = lane + 64 * i;
         mu.v[i] = e < d ? a.cav_mu[(size_t)k * d + e] : 0.0;
@@ -122,92 +104,21 @@ k_nuts(NutsArgs a) {
         mq.v[i] = 0; mp.v[i] = 0; mg.v[i] = 0; rho.v[i] = 0; psp.v[i] = 0; psm.v[i] = 0;
         n_rho.v[i] = 0; n_psl.v[i] = 0; bq.v[i] = 0; bg.v[i] = 0; psr.v[i] = 0;
     }
-    // initial position (method.py:159 init / :404-406 init_prev)
     {
         const double *lastp = a.last + ((size_t)k * a.chains + chain) * P;
-        FORV {
-            const int e = lane + 64 * i;
-            double q0 = 0.0;
-            if (e < P) {
-                if (a.init_mode == 2) q0 = lastp[e];
-                else if (a.init_mode == 0) {
-                    double u1, u2;
-                    rng_u2(key, 0, K_INIT, (uint32_t)(e >> 1), 0, u1, u2);
-                    q0 = -2.0 + 4.0 * ((e & 1) ? u2 : u1);
-                }
-            }
-            qs.v[i] = q0;
-        }
+        FORV { const int e = lane + 64 * i; double q0; EPX_INIT_POSITION(q0, e, lastp) qs.v[i] = q0; }
     }
-    // adaptation state (stepsize_adaptation.hpp / windowed_adaptation.hpp @ Stan 2.17)
-    const double DELTA = 0.8, GAMMA = 0.05, T0 = 10.0, KAPPA = 0.75, LOG08 = -0.2231435513142097558;
-    double eps = 1.0, da_mu = log(10.0), s_bar = 0, x_bar = 0, da_count = 0;
-    int va_init_buf = 75, va_term = 50, va_base = 25;
-    if (va_init_buf + va_base + va_term > a.warmup && a.warmup >= 20) {
-        va_init_buf = (int)(0.15 * a.warmup);
-        va_term = (int)(0.1 * a.warmup);
-        va_base = a.warmup - (va_init_buf + va_term);
-    }
-    int va_counter = 0, va_wsize = va_base, va_next = va_init_buf + va_base - 1;
-    double va_n = 0;
-    // statistics
-    double eps_sum = 0, acc_sum = 0, depth_sum = 0, nleap_tot = 0, ngrad = 0;
-    int ndiv = 0, npost = 0, kept = 0, failed = 0;
-    // transition state
-    int t = 0, mode = MODE_INIT, depth = 0, leaf = 0, nleaf = 1, fwd = 1, nleap = 0, divergent = 0, init_try = 0;
-    int ss_trial = 0, ss_dir = 0, ss_after_update = 0;
-    uint32_t ss_t = 0;
-    double H0 = 0, lsw = 0, sum_metro = 0, eps_l = 0;
+#include "nuts_chain_state.inc"
     int parity = 0;
-    // Batched random numbers: lane x of u_dir holds DIR(depth x) for x < 16 and TOP(depth x-16)
-    // for 16 <= x < 32 of the current transition; lane x of gum holds the Gumbel variate
-    // -log(-log u) of leaf (leaf & ~63) + x of the current doubling.
-    double u_dir = 0.0, gum = 0.0;
-    // Leaf energy errors dH of the current doubling, lane (leaf & 63); reduced 64 at a time into
-    // the running log-sum-weight (lw_m + log lw_s) and the accept statistic.
-    double dhb = 0.0, lw_m = -INFINITY, lw_s = 0.0;
 
     FORV { zq.v[i] = qs.v[i]; }
-    const bool teacher = a.eps_in != nullptr;       // fixed step size / metric (test hook)
-    if (teacher) {
-        eps = a.eps_in[(size_t)sb * a.chains + chain];
-        if (a.inv_e_in) {
-            const double *ie = a.inv_e_in + ((size_t)sb * a.chains + chain) * P;
-            FORV { const int e = lane + 64 * i; if (e < P) inv_e.v[i] = ie[e]; }
-        }
-    }
-    // opt-in carried adaptation: last call's step size of the chain, the site's pooled sample variances
-    const bool carry = !teacher && a.carry_eps != nullptr && a.carry_eps[(size_t)k * a.chains + chain] > 0.0;
-    if (carry) {
-        eps = a.carry_eps[(size_t)k * a.chains + chain];
-        da_mu = log(10.0 * eps);
-        const double *cm = a.carry_metric + (size_t)k * P;
-        FORV { const int e = lane + 64 * i; if (e < P) inv_e.v[i] = cm[e]; }
-    }
+    EPX_LOAD_TEACHER_CARRY(true, lane, P)
     const uint32_t toff = (uint32_t)a.t_offset + 1u;
+    auto flush_dh = [&](int cnt) { flush_leaf_dh<false>(lane, cnt, dhb, lw_m, lw_s, sum_metro); };
 
-    // reduce the buffered leaf energy errors (lanes 0..cnt-1 of dhb)
-    auto flush_dh = [&](int cnt) {
-        const bool ok = lane < cnt;
-        const double dh = ok ? dhb : -INFINITY;
-        const double mb = wave_max(dh);
-        const double m_new = fmax(lw_m, mb);
-        double w = 0.0, me = 0.0;
-        if (ok) {
-            w = (m_new == -INFINITY) ? 0.0 : exp(dh - m_new);
-            me = dh > 0 ? 1.0 : exp(dh);
-        }
-        wave_sum2(w, me);
-        const double scale = (lw_m == -INFINITY) ? 0.0 : exp(lw_m - m_new);
-        lw_s = lw_s * scale + w;
-        lw_m = m_new;
-        sum_metro += me;
-    };
 
 #ifdef EPX_STAMPS
-    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tprev = __builtin_amdgcn_s_memtime();
-    __builtin_amdgcn_s_waitcnt(0xC07F);
+    STAMP_INIT;                   // (under #ifdef: outside the diagnostic build even its empty statement changes the kernel's code)
 #endif
     for (;;) {
         STAMP(6);
@@ -235,27 +146,7 @@ k_nuts(NutsArgs a) {
         a.stamps[(size_t)blockIdx.x * 8 + 7] = (unsigned long long)ngrad;
     }
 #endif
-    if (wt == 0) {
-        double *lastp = a.last + ((size_t)k * a.chains + chain) * P;
-        FORV { const int e = lane + 64 * i; if (e < P) lastp[e] = qs.v[i]; }
-        if (failed) {
-            for (int kk = 0; kk < a.nkeep; ++kk) {
-                double *dst = a.draws + (((size_t)k * a.chains + chain) * a.nkeep + kk) * P;
-                FORV { const int e = lane + 64 * i; if (e < P) dst[e] = qs.v[i]; }
-            }
-        }
-        if (lane == 0) {
-            double *st = a.chain_stats + ((size_t)k * a.chains + chain) * ST_COUNT;
-            st[ST_STEPSIZE_MEAN] = a.iter > 0 && !failed ? eps_sum / a.iter : 0.0;
-            st[ST_STEPSIZE_FINAL] = eps;
-            st[ST_NLEAP] = nleap_tot;
-            st[ST_NGRAD] = ngrad;
-            st[ST_NDIV] = ndiv;
-            st[ST_ACCEPT_MEAN] = npost ? acc_sum / npost : 0.0;
-            st[ST_DEPTH_MEAN] = npost ? depth_sum / npost : 0.0;
-            st[ST_FAIL] = failed;
-        }
-    }
+    if (wt == 0) EPX_WRITE_CHAIN_RECORD(lane, P, P)
 }
 
 // ---------------------------------------------------------------------------
@@ -443,79 +334,22 @@ k_nuts_spec(NutsArgs a) {
     auto st_stk = [&](int l, int v, int i, double x) { const int off = l * SREC + (v * NV + i) * 64 + lane; if constexpr (STL) stk_l[off] = x; else stk_g[off] = x; };
     const RngKey key = make_key((uint64_t)a.seeds[sb], chain);
     V qs, gs, pq, pp, pg, mq, mp, mg, rho, psp, psm, wmean, wm2, bq, bg, sent_e, in_q, in_p, in_g;
-    double lps = 0, plp = 0, mlp = 0, b_key = 0, b_plp = 0;
+    double lps = 0, plp = 0, mlp = 0, b_key = 0, b_plp = 0;       // (here, not in nuts_chain_state.inc: EPX_CHAIN_HEAD_DECLARED)
     FORV {
         bq.v[i] = 0; bg.v[i] = 0; wmean.v[i] = 0.0; wm2.v[i] = 0.0; gs.v[i] = 0; pq.v[i] = 0; pp.v[i] = 0; pg.v[i] = 0;
         mq.v[i] = 0; mp.v[i] = 0; mg.v[i] = 0; rho.v[i] = 0; psp.v[i] = 0; psm.v[i] = 0;
     }
     {
         const double *lastp = a.last + ((size_t)k * a.chains + chain) * a.P;
-        FORV {
-            const int e = lane + 64 * i;
-            double q0 = 0.0;
-            if (e < P) {
-                if (a.init_mode == 2) q0 = lastp[e];
-                else if (a.init_mode == 0) {
-                    double u1, u2;
-                    rng_u2(key, 0, K_INIT, (uint32_t)(e >> 1), 0, u1, u2);
-                    q0 = -2.0 + 4.0 * ((e & 1) ? u2 : u1);
-                }
-            }
-            qs.v[i] = q0;
-        }
+        FORV { const int e = lane + 64 * i; double q0; EPX_INIT_POSITION(q0, e, lastp) qs.v[i] = q0; }
     }
-    const double DELTA = 0.8, GAMMA = 0.05, T0 = 10.0, KAPPA = 0.75, LOG08 = -0.2231435513142097558;
-    double eps = 1.0, da_mu = log(10.0), s_bar = 0, x_bar = 0, da_count = 0;
-    int va_init_buf = 75, va_term = 50, va_base = 25;
-    if (va_init_buf + va_base + va_term > a.warmup && a.warmup >= 20) {
-        va_init_buf = (int)(0.15 * a.warmup);
-        va_term = (int)(0.1 * a.warmup);
-        va_base = a.warmup - (va_init_buf + va_term);
-    }
-    int va_counter = 0, va_wsize = va_base, va_next = va_init_buf + va_base - 1;
-    double va_n = 0;
-    double eps_sum = 0, acc_sum = 0, depth_sum = 0, nleap_tot = 0, ngrad = 0;
-    int ndiv = 0, npost = 0, kept = 0, failed = 0;
-    int t = 0, mode = MODE_INIT, depth = 0, leaf = 0, nleaf = 1, fwd = 1, nleap = 0, divergent = 0, init_try = 0;
-    int ss_trial = 0, ss_dir = 0, ss_after_update = 0;
-    uint32_t ss_t = 0;
-    double H0 = 0, lsw = 0, sum_metro = 0;
-    double u_dir = 0.0, gum = 0.0;
-    double dhb = 0.0, lw_m = -INFINITY, lw_s = 0.0;
+#define EPX_CHAIN_HEAD_DECLARED
+#include "nuts_chain_state.inc"
+#undef EPX_CHAIN_HEAD_DECLARED
     FORV { zq.v[i] = qs.v[i]; }
-    const bool teacher = a.eps_in != nullptr;
-    if (teacher) {
-        eps = a.eps_in[(size_t)sb * a.chains + chain];
-        if (a.inv_e_in) {
-            const double *ie = a.inv_e_in + ((size_t)sb * a.chains + chain) * a.P;
-            FORV { const int e = lane + 64 * i; if (e < P) inv_e.v[i] = ie[e]; }
-        }
-    }
-    // opt-in carried adaptation: last call's step size of the chain, the site's pooled sample variances
-    const bool carry = !teacher && a.carry_eps != nullptr && a.carry_eps[(size_t)k * a.chains + chain] > 0.0;
-    if (carry) {
-        eps = a.carry_eps[(size_t)k * a.chains + chain];
-        da_mu = log(10.0 * eps);
-        const double *cm = a.carry_metric + (size_t)k * a.P;
-        FORV { const int e = lane + 64 * i; if (e < P) inv_e.v[i] = cm[e]; }
-    }
+    EPX_LOAD_TEACHER_CARRY(true, lane, a.P)
     const uint32_t toff = (uint32_t)a.t_offset + 1u;
-    auto flush_dh = [&](int cnt) {
-        const bool ok = lane < cnt;
-        const double dh = ok ? dhb : -INFINITY;
-        const double mb = wave_max(dh);
-        const double m_new = fmax(lw_m, mb);
-        double w = 0.0, me = 0.0;
-        if (ok) {
-            w = (m_new == -INFINITY) ? 0.0 : exp(dh - m_new);
-            me = dh > 0 ? 1.0 : exp(dh);
-        }
-        wave_sum2(w, me);
-        const double scale = (lw_m == -INFINITY) ? 0.0 : exp(lw_m - m_new);
-        lw_s = lw_s * scale + w;
-        lw_m = m_new;
-        sum_metro += me;
-    };
+    auto flush_dh = [&](int cnt) { flush_leaf_dh<false>(lane, cnt, dhb, lw_m, lw_s, sum_metro); };
     // post the integration state the GWs have to continue from (stamp = interval)
     double sent_eps = 0.0;
     auto post = [&](int stamp, int cmd) {
@@ -573,27 +407,7 @@ k_nuts_spec(NutsArgs a) {
 #ifdef EPX_STAMPS
     if (a.stamps && lane == 0) a.stamps[(size_t)blockIdx.x * 8 + 6] = bk_busy;
 #endif
-    {
-        double *lastp = a.last + ((size_t)k * a.chains + chain) * a.P;
-        FORV { const int e = lane + 64 * i; if (e < P) lastp[e] = qs.v[i]; }
-        if (failed) {
-            for (int kk = 0; kk < a.nkeep; ++kk) {
-                double *dst = a.draws + (((size_t)k * a.chains + chain) * a.nkeep + kk) * a.P;
-                FORV { const int e = lane + 64 * i; if (e < P) dst[e] = qs.v[i]; }
-            }
-        }
-        if (lane == 0) {
-            double *st = a.chain_stats + ((size_t)k * a.chains + chain) * ST_COUNT;
-            st[ST_STEPSIZE_MEAN] = a.iter > 0 && !failed ? eps_sum / a.iter : 0.0;
-            st[ST_STEPSIZE_FINAL] = eps;
-            st[ST_NLEAP] = nleap_tot;
-            st[ST_NGRAD] = ngrad;
-            st[ST_NDIV] = ndiv;
-            st[ST_ACCEPT_MEAN] = npost ? acc_sum / npost : 0.0;
-            st[ST_DEPTH_MEAN] = npost ? depth_sum / npost : 0.0;
-            st[ST_FAIL] = failed;
-        }
-    }
+    EPX_WRITE_CHAIN_RECORD(lane, P, a.P)
 }
 
 // ---------------------------------------------------------------------------

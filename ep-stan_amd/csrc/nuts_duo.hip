@@ -108,8 +108,6 @@ __device__ inline void relay_step() {
 //   chains < 4 / failed-chain cases of tests/test_gpu_round3.py run every one of them.
 __device__ inline void team_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ inline double mfma4(double a, double b, double c) { return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0); }
-__device__ inline void ck_assign(GScal &x, double v) { x = v; }
-__device__ inline void ck_assign(RScal &x, double v) { x = v; }
 // everything this wave wrote to LDS is visible before the flag that follows
 __device__ inline void duo_publish(duo_flag_t *flag, int v) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -124,35 +122,9 @@ __device__ inline void duo_publish_c(duo_flag_t *flag, int v) {
     else duo_publish(flag, v);
 }
 
-// In-kernel cycle stamps exist only in the diagnostic build (-DEPX_STAMPS); its run time is never
-// quoted, only the shares.  Slots per workgroup (chain 0): state wave 0 prep / 1 bookkeeping /
-// 2 cavity term / 3 waiting for the row waves / 4 chain rule; row wave 5 waiting for a job / 6 row pass;
+// Slots of the in-kernel cycle stamps (diagnostic build, nuts_common.h) per workgroup (chain 0): state wave 0 prep /
+// 1 bookkeeping / 2 cavity term / 3 waiting for the row waves / 4 chain rule; row wave 5 waiting for a job / 6 row pass;
 // 7 = leapfrogs
-#ifdef EPX_STAMPS
-#define STAMP(i)                                                                   \
-    do {                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-        unsigned long long t_ = __builtin_amdgcn_s_memtime();                      \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                        \
-        tacc[i] += t_ - tprev; tprev = t_;                                         \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-    } while (0)
-#define STAMP_INIT unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long tprev = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F)
-#define TSTAMP(i)                                                                  \
-    do {                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-        unsigned long long t_ = __builtin_amdgcn_s_memtime();                      \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                        \
-        tdet[i] += t_ - tprev2; tprev2 = t_;                                       \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-    } while (0)
-#define TSTAMP_INIT unsigned long long tdet[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long tprev2 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F)
-#else
-#define STAMP(i) do { } while (0)
-#define STAMP_INIT do { } while (0)
-#define TSTAMP(i) do { } while (0)
-#define TSTAMP_INIT do { } while (0)
-#endif
 
 typedef const __attribute__((address_space(4))) NutsArgs DuoArgsK;       // the kernel arguments where they are: kernarg segment
 
@@ -808,18 +780,13 @@ __device__ __forceinline__ void duo_piece(DuoArgsK *kargs_p, int tid, bool queue
     // The 13 vectors that change once per subtree / transition (current sample and its gradient, both
     // tree ends, rho, p-sharps, Welford sums): registers, or (COLD) a per-chain store in global memory --
     // at two registers per vector they are 52 VGPRs that the state wave spilled to scratch
-    using CV = typename std::conditional<COLD, GVec, V>::type;
+    using CV = typename std::conditional<COLD, GVec<true>, V>::type;
     V mu, inv_e, zq, zp, zg;
     CV qs, gs, pq, pp, pg, mq, mp, mg, rho, psp, psm, wmean, wm2, bq, bg;
     gdouble *cold = COLD ? stk_g + g_stack : nullptr;
     auto bind = [&](CV &x, int which, int ln) {
         if constexpr (COLD) { x.v.b = cold + (size_t)which * NV * 64; x.v.lane = ln; x.v.len = P; }
     };
-#define EPX_BIND_COLD(ln)                                                                              \
-    bind(qs, GV_QS, ln); bind(gs, GV_GS, ln); bind(pq, GV_PQ, ln); bind(pp, GV_PP, ln); bind(pg, GV_PG, ln); \
-    bind(mq, GV_MQ, ln); bind(mp, GV_MP, ln); bind(mg, GV_MG, ln); bind(rho, GV_RHO, ln);                 \
-    bind(psp, GV_PSP, ln); bind(psm, GV_PSM, ln); bind(wmean, GV_WMEAN, ln); bind(wm2, GV_WM2, ln); \
-    bind(bq, GV_BQ, ln); bind(bg, GV_BG, ln)
     EPX_BIND_COLD(lane);
     // the scalars that are touched once per transition (COLD: in the chain's global store, see GScal)
     using CS = typename std::conditional<COLD, GScal, RScal>::type;
@@ -830,9 +797,8 @@ __device__ __forceinline__ void duo_piece(DuoArgsK *kargs_p, int tid, bool queue
         eps_sum.p = sc0 + 6; acc_sum.p = sc0 + 7; depth_sum.p = sc0 + 8; nleap_tot.p = sc0 + 9;
         plp.p = sc0 + 10; mlp.p = sc0 + 11; b_plp.p = sc0 + 12; lsw.p = sc0 + 13; t_end_c.p = sc0 + 14;
     }
-    lps = 0.0; plp = 0.0; mlp = 0.0; b_plp = 0.0; lsw = 0.0;
+    lps = 0.0; plp = 0.0; mlp = 0.0; b_plp = 0.0; lsw = 0.0;      // (the other nine: nuts_chain_state.inc)
     t_end_c = (double)t_end;                      // (read once per transition)
-    double zlp = 0, b_key = 0;
     FORV {
         const int e = lane + 64 * i;
         mu.v[i] = e < d ? a.cav_mu[(size_t)k * d + e] : 0.0;
@@ -846,77 +812,24 @@ __device__ __forceinline__ void duo_piece(DuoArgsK *kargs_p, int tid, bool queue
     if (resume) {
         // the sample and the Welford sums of the piece before this one (checkpoint record: qs, wmean, wm2, metric, scalars)
         double *ckp = ck_rec(t_begin);
-        FORV {
-            qs.v[i] = ck_load(ckp + (0 * NV + i) * 64 + lane);
-            wmean.v[i] = ck_load(ckp + (1 * NV + i) * 64 + lane);
-            wm2.v[i] = ck_load(ckp + (2 * NV + i) * 64 + lane);
-        }
+        FORV { EPX_CK_RESTORE_SAMPLE(ckp, lane, qs.v[i]); }
     } else {
         FORV { wmean.v[i] = 0.0; wm2.v[i] = 0.0; }
     }
     if (!resume) {
         const double *lastp = a.last + ((size_t)k * a.chains + chain) * P;
-        FORV {
-            const int e = lane + 64 * i;
-            double q0 = 0.0;
-            if (e < P) {
-                if (a.init_mode == 2) q0 = lastp[e];
-                else if (a.init_mode == 0) {
-                    double u1, u2;
-                    rng_u2(key, 0, K_INIT, (uint32_t)(e >> 1), 0, u1, u2);
-                    q0 = -2.0 + 4.0 * ((e & 1) ? u2 : u1);
-                }
-            }
-            qs.v[i] = q0;
-        }
+        FORV { const int e = lane + 64 * i; double q0; EPX_INIT_POSITION(q0, e, lastp) qs.v[i] = q0; }
     }
-    // adaptation state (stepsize_adaptation.hpp / windowed_adaptation.hpp @ Stan 2.17)
-    const double DELTA = 0.8, GAMMA = 0.05, T0 = 10.0, KAPPA = 0.75, LOG08 = -0.2231435513142097558;
-    double eps = 1.0;
-    da_mu = log(10.0); s_bar = 0.0; x_bar = 0.0; da_count = 0.0;
-    int va_init_buf = 75, va_term = 50, va_base = 25;
-    if (va_init_buf + va_base + va_term > a.warmup && a.warmup >= 20) {
-        va_init_buf = (int)(0.15 * a.warmup);
-        va_term = (int)(0.1 * a.warmup);
-        va_base = a.warmup - (va_init_buf + va_term);
-    }
-    int va_counter = 0, va_wsize = va_base, va_next = va_init_buf + va_base - 1;
-    va_n = 0.0;
-    eps_sum = 0.0; acc_sum = 0.0; depth_sum = 0.0; nleap_tot = 0.0;
-    double ngrad = 0;
-    int ndiv = 0, npost = 0, kept = 0, failed = 0;
-    int t = 0, mode = MODE_INIT, depth = 0, leaf = 0, nleaf = 1, fwd = 1, nleap = 0, divergent = 0, init_try = 0;
-    int ss_trial = 0, ss_dir = 0, ss_after_update = 0;
-    uint32_t ss_t = 0;
-    double H0 = 0, sum_metro = 0, eps_l = 0;
-    double u_dir = 0.0, gum = 0.0;
-    double dhb = 0.0, lw_m = -INFINITY, lw_s = 0.0;
+#define EPX_CHAIN_SCALARS_BOUND
+#include "nuts_chain_state.inc"
+#undef EPX_CHAIN_SCALARS_BOUND
     int bail = 0;
     FORV { zq.v[i] = qs.v[i]; }
-    const bool teacher = a.eps_in != nullptr;       // fixed step size / metric (test hook)
-    if (teacher) {
-        eps = a.eps_in[(size_t)sb * a.chains + chain];
-        if (a.inv_e_in) {
-            const double *ie = a.inv_e_in + ((size_t)sb * a.chains + chain) * P;
-            FORV { const int e = lane + 64 * i; if (e < P) inv_e.v[i] = ie[e]; }
-        }
-    }
-    // opt-in carried adaptation: last call's step size of the chain, the site's pooled sample variances
-    const bool carry = !teacher && a.carry_eps != nullptr && a.carry_eps[(size_t)k * a.chains + chain] > 0.0;
-    if (carry) {
-        eps = a.carry_eps[(size_t)k * a.chains + chain];
-        da_mu = log(10.0 * eps);
-        const double *cm = a.carry_metric + (size_t)k * P;
-        FORV { const int e = lane + 64 * i; if (e < P) inv_e.v[i] = cm[e]; }
-    }
+    EPX_LOAD_TEACHER_CARRY(true, lane, P)
     if constexpr (COLD) {
         if (resume) {
             double *ckp = ck_rec(t_begin);
-            FORV inv_e.v[i] = ck_load(ckp + (3 * NV + i) * 64 + lane);
-            const double ckv = ck_load(ckp + 4 * NV * 64 + lane);
-#define EPX_CK_GET(idx, x) ck_assign(x, readlane_d(ckv, idx));
-            EPX_CK_LIST(EPX_CK_GET)
-#undef EPX_CK_GET
+            EPX_CK_RESTORE_STATE(ckp, lane)
             ngrad -= 1.0;                             // the gradient at the restored sample is evaluated once more
             if (failed) {                             // it failed in its first piece, where everything was written:
                 // hand the mark on to the piece after this one (every boundary has its own record), and leave
@@ -929,26 +842,8 @@ __device__ __forceinline__ void duo_piece(DuoArgsK *kargs_p, int tid, bool queue
         }
     }
     const uint32_t toff = (uint32_t)a.t_offset + 1u;
-    // (row team: the subtree-level elementary functions are the lean ones -- a wave that completes a subtree keeps the three
-    // other chains and the row team waiting at the pass's barrier, and libm's exp / log are ~10 x the instructions)
-#define SM_EXP(x) (TEAM ? exp_d(x) : exp(x))
-    auto flush_dh = [&](int cnt) {
-        const bool ok = lane < cnt;
-        const double dh = ok ? dhb : -INFINITY;
-        const double mb = wave_max(dh);
-        const double m_new = fmax(lw_m, mb);
-        double w = 0.0, me = 0.0;
-        if (ok) {
-            w = (m_new == -INFINITY) ? 0.0 : SM_EXP(dh - m_new);
-            me = dh > 0 ? 1.0 : SM_EXP(dh);
-        }
-        wave_sum2(w, me);
-        const double scale = (lw_m == -INFINITY) ? 0.0 : SM_EXP(lw_m - m_new);
-        lw_s = lw_s * scale + w;
-        lw_m = m_new;
-        sum_metro += me;
-    };
-#undef SM_EXP
+    // (row team: the lean exp, see flush_leaf_dh)
+    auto flush_dh = [&](int cnt) { flush_leaf_dh<TEAM>(lane, cnt, dhb, lw_m, lw_s, sum_metro); };
 
     if constexpr (BKW) {
         if (is_bk) {
@@ -1572,42 +1467,12 @@ __device__ __forceinline__ void duo_piece(DuoArgsK *kargs_p, int tid, bool queue
             // ---- checkpoint at the transition boundary: the sample, the Welford sums, the metric and the scalars of
             // EPX_CK_LIST (the gradient at the sample is re-evaluated by the piece that continues)
             double *ckp = ck_rec(t_end);
-            FORV {
-                ck_store(ckp + (0 * NV + i) * 64 + lane, qs.v[i]);
-                ck_store(ckp + (1 * NV + i) * 64 + lane, wmean.v[i]);
-                ck_store(ckp + (2 * NV + i) * 64 + lane, wm2.v[i]);
-                ck_store(ckp + (3 * NV + i) * 64 + lane, inv_e.v[i]);
-            }
-            double ckv = 0.0;
-#define EPX_CK_PUT(idx, x) ckv = lane == (idx) ? (double)(x) : ckv;
-            EPX_CK_LIST(EPX_CK_PUT)
-#undef EPX_CK_PUT
-            ck_store(ckp + 4 * NV * 64 + lane, ckv);
+            EPX_CK_SAVE(ckp, lane)
             piece_checkpoint_out();                                 // the record is out before the site is put back
         }
     }
     if (!failed && t < a.iter) return;          // suspended at the end of a piece: no final record yet
-    {
-        double *lastp = a.last + ((size_t)k * a.chains + chain) * P;
-        FORV { const int e = lane + 64 * i; if (e < P) lastp[e] = qs.v[i]; }
-        if (failed) {
-            for (int kk = 0; kk < a.nkeep; ++kk) {
-                double *dst = a.draws + (((size_t)k * a.chains + chain) * a.nkeep + kk) * P;
-                FORV { const int e = lane + 64 * i; if (e < P) dst[e] = qs.v[i]; }
-            }
-        }
-        if (lane == 0) {
-            double *st = a.chain_stats + ((size_t)k * a.chains + chain) * ST_COUNT;
-            st[ST_STEPSIZE_MEAN] = a.iter > 0 && !failed ? eps_sum / a.iter : 0.0;
-            st[ST_STEPSIZE_FINAL] = eps;
-            st[ST_NLEAP] = nleap_tot;
-            st[ST_NGRAD] = ngrad;
-            st[ST_NDIV] = ndiv;
-            st[ST_ACCEPT_MEAN] = npost ? acc_sum / npost : 0.0;
-            st[ST_DEPTH_MEAN] = npost ? depth_sum / npost : 0.0;
-            st[ST_FAIL] = failed;
-        }
-    }
+    EPX_WRITE_CHAIN_RECORD(lane, P, P)
 }
 #undef a
 

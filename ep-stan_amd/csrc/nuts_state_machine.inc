@@ -1,9 +1,16 @@
 // Tree bookkeeping, adaptation and transition control of the NUTS kernels: the part of one
-// loop iteration that follows the gradient evaluation.  Textually included by k_nuts
-// (nuts.hip) and k_nuts_stream (nuts_stream.hip) so both kernels run the SAME algorithm.
-// Expects in scope: the chain state (Vec<NV> vectors, scalars), zlp, kin, lambdas ld_stk(level, vector, register) /
-// st_stk(level, vector, register, value) / flush_dh, and the macros EPX_CHAIN_EXIT (leave the chain loop) and EPX_DBG_EXIT
-// (leave after the test hook wrote the initial gradient).
+// loop iteration that follows the gradient evaluation.  Textually included by every sampler kernel -- k_nuts and
+// k_nuts_spec's bookkeeping wave (nuts.hip), duo_piece's state wave and its bookkeeping wave (nuts_duo.hip),
+// stream_piece (nuts_stream.hip) -- so all of them run the SAME algorithm.
+// Its scope is the one nuts_chain_state.inc declares (the chain's scalars with their start values: the list is at
+// the top of that file); the macro it uses (EPX_INIT_DRAW) is in nuts_common.h.  The kernel itself provides:
+//   the vectors, Vec<NV> or anything with the same `.v[i]`: mu-free state inv_e qs gs zq zp zg, tree ends pq pp pg mq mp mg,
+//       rho psp psm, Welford sums wmean wm2, the subtree's best bq bg, and the iteration-local n_rho n_psl psr;
+//   kin: kinetic energy of the state just evaluated (its log density is zlp); carry, teacher, toff; lane, wt (the wave of the chain that writes records: wt == 0), P, k, sb,
+//       chain, key and the arguments `a`;
+//   lambdas ld_stk(level, vector, register) / st_stk(level, vector, register, value) / flush_dh(count);
+//   the macros EPX_CHAIN_EXIT (leave the chain loop), EPX_DBG_EXIT (leave after the test hook wrote the initial
+//       gradient) and STAMP_LEAF.
 // Optional: EPX_RESUME (bool: the chain continues an earlier piece of its run -- the initial evaluation goes
 // straight to the next transition) and EPX_T_END (the transition at which this piece ends; default a.iter).
 #ifndef EPX_WAVE_SUM2
@@ -143,17 +150,12 @@
             if (!fin && a.init_mode == 0 && !teacher && !EPX_RESUME && init_try < 99) {
                 // init = 'random': Stan draws the start again, up to 100 times, until log density and gradient are finite
                 // (stan::services::util::initialize behind PyStan's sampling(), /root/reference/epstan/util.py:716);
-                // a given start -- zeros, the previous draws -- gets one attempt.  Draw r of the chain is the Philox
-                // stream of the first one with r in its last counter word.
+                // a given start -- zeros, the previous draws -- gets one attempt.
                 ++init_try;
                 FORV {
                     const int e = lane + 64 * i;
                     double q0 = 0.0;
-                    if (e < P) {
-                        double u1, u2;
-                        rng_u2(key, 0, K_INIT, (uint32_t)(e >> 1), (uint32_t)init_try, u1, u2);
-                        q0 = -2.0 + 4.0 * ((e & 1) ? u2 : u1);
-                    }
+                    if (e < P) EPX_INIT_DRAW(q0, e, init_try)
                     qs.v[i] = q0; zq.v[i] = q0; zp.v[i] = 0.0; zg.v[i] = 0.0;
                 }
                 eps_l = 0.0;                            // (the next "leapfrog" is the evaluation at the new start)

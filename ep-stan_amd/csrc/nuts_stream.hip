@@ -20,48 +20,17 @@
 //   * the parameter transforms gather through LDS copies of q and exp(q).
 // Algorithmic HBM bytes per leapfrog of one site: n_j*D*8 + n_j*4 + d*d*8 (X, y, Omega), for
 // min(chains, 4) gradients.
-#include "epx_device.h"
-#include "epx_kernels.h"
+#include "nuts_common.h"
 #include "epx_stream_tile.h"
 #include "epx_pieces.h"
 #include <type_traits>
 
 namespace epx {
 
-template <int NV> struct VecS { double v[NV]; };
-#define FORV _Pragma("unroll") for (int i = 0; i < NV; ++i)
-// In-kernel cycle stamps exist only in the diagnostic build (-DEPX_STAMPS); its run time is
-// never quoted, only the shares of the segments (scripts/stamps_stream.py).
-#ifdef EPX_STAMPS
-#define STAMP(i)                                                                   \
-    do {                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-        unsigned long long t_ = __builtin_amdgcn_s_memtime();                      \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                        \
-        tacc[i] += t_ - tprev; tprev = t_;                                         \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-    } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
-
-// cold-store vector: same `.v[i]` syntax as VecS, backed by global memory
-struct ColdRef {
-    gdouble *p;
-    __device__ operator double() const { return *p; }
-    __device__ const ColdRef &operator=(double x) const { *p = x; return *this; }
-    __device__ const ColdRef &operator=(const ColdRef &o) const { const double x = *o.p; *p = x; return *this; }
-    __device__ const ColdRef &operator+=(double x) const { *p = *p + x; return *this; }
-};
-// b is wave-uniform (scalar registers), so every access is `saddr + lane*8 + immediate`
-struct ColdIdx { gdouble *b; int lane; __device__ ColdRef operator[](int i) const { return ColdRef{b + (lane + 64 * i)}; } };
-struct ColdV { ColdIdx v; };
-enum { CV_QS, CV_GS, CV_PQ, CV_PP, CV_PG, CV_MQ, CV_MP, CV_MG, CV_RHO, CV_PSP, CV_PSM, CV_WMEAN, CV_WM2, CV_BQ, CV_BG, CV_COUNT };
-
-enum { SMODE_INIT = 0, SMODE_SS = 1, SMODE_TREE = 2 };
-#define MODE_INIT SMODE_INIT
-#define MODE_SS SMODE_SS
-#define MODE_TREE SMODE_TREE
+// In-kernel cycle stamps of the diagnostic build: nuts_common.h; the shares of the segments by scripts/stamps_stream.py.
+// The cold-store vectors are GVec<false> (nuts_common.h): whole 64-lane rows, no masking by length, and no line of
+// scalars behind the vectors.
+constexpr int COLD_VECS = GV_SCAL;
 
 #ifndef EPX_STREAM_WAVE_SCALAR
 #define EPX_STREAM_WAVE_SCALAR 2
@@ -87,10 +56,10 @@ __device__ __forceinline__ void stream_piece(StreamArgsK *kargs_p, int q_site, i
     const int q_len = queued ? piece_len_at(a, q_site, q_t0) : 0;
     const int t_end = queued ? (q_t0 + q_len < a.iter ? q_t0 + q_len : a.iter) : a.iter;
     const bool resume = t_begin > 0;
-    using V = VecS<NV>;
+    using V = Vec<NV>;
     constexpr int NT = RES ? 256 : STREAM_THREADS;
     // register vectors when they fit (NV <= 2: 23 x 4 VGPRs), cold store otherwise
-    using CV = typename std::conditional<(RES && NV <= 2), VecS<NV>, ColdV>::type;
+    using CV = typename std::conditional<(RES && NV <= 2), V, GVec<false>>::type;
     constexpr int SREC = nuts_stack_record(NV); // per-level stack record (doubles)
     constexpr int PMAX = 64 * NV;
 
@@ -182,14 +151,8 @@ __device__ __forceinline__ void stream_piece(StreamArgsK *kargs_p, int q_site, i
     const size_t chain_slot = (size_t)(queued ? (int)blockIdx.x : sb) * a.chains + (active ? chain : 0);
     double *ckp = queued ? piece_record(a, sb, t_begin, active ? chain : 0, NV) : nullptr;            // the record this piece starts from
     double *ckp_out = queued ? piece_record(a, sb, t_end, active ? chain : 0, NV) : nullptr;        // ... and the one it leaves
-    // wave-uniform base pointers (held in scalar registers; lanes add lane*8)
-    auto uniform_ptr = [](double *p) -> gdouble * {
-        const unsigned long long u = (unsigned long long)p;
-        const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)u);
-        const unsigned hi32 = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-        return reinterpret_cast<gdouble *>((uintptr_t)(((unsigned long long)hi32 << 32) | lo32));
-    };
-    gdouble *stk_g = uniform_ptr(a.stack + chain_slot * ((size_t)a.max_depth * SREC + (size_t)CV_COUNT * PMAX));
+    // wave-uniform base pointers (held in scalar registers; lanes add lane*8); the cold store: GV_SCAL vectors, no scalar line
+    gdouble *stk_g = uniform_ptr(a.stack + chain_slot * ((size_t)a.max_depth * SREC + (size_t)COLD_VECS * PMAX));
     gdouble *cold = stk_g + (size_t)a.max_depth * SREC;
     int stk_lane = lane0;               // (the loop's opaque copy of the lane index: set at the top of every iteration)
     auto ld_stk = [&](int l, int v, int i) -> double { return stk_g[l * SREC + (v * NV + i) * 64 + stk_lane]; };
@@ -202,15 +165,9 @@ __device__ __forceinline__ void stream_piece(StreamArgsK *kargs_p, int q_site, i
     V inv_e, zq, zp, zg;                                                // registers, live across leapfrogs
     CV qs, gs, pq, pp, pg, mq, mp, mg, rho, psp, psm, wmean, wm2, bq, bg;   // cold store (or registers, see CV)
     auto bind = [&](CV &x, int which, int ln) {
-        if constexpr (std::is_same<CV, ColdV>::value) { x.v.b = cold + which * PMAX; x.v.lane = ln; }
+        if constexpr (!std::is_same<CV, V>::value) { x.v.b = cold + which * PMAX; x.v.lane = ln; }
     };
-#define EPX_BIND_COLD(ln)                                                                              \
-    bind(qs, CV_QS, ln); bind(gs, CV_GS, ln); bind(pq, CV_PQ, ln); bind(pp, CV_PP, ln); bind(pg, CV_PG, ln); \
-    bind(mq, CV_MQ, ln); bind(mp, CV_MP, ln); bind(mg, CV_MG, ln); bind(rho, CV_RHO, ln);                 \
-    bind(psp, CV_PSP, ln); bind(psm, CV_PSM, ln); bind(wmean, CV_WMEAN, ln); bind(wm2, CV_WM2, ln); \
-    bind(bq, CV_BQ, ln); bind(bg, CV_BG, ln)
     EPX_BIND_COLD(lane0);
-    double lps = 0, zlp = 0, plp = 0, mlp = 0, b_key = 0, b_plp = 0;
     FORV {
         inv_e.v[i] = 1.0;
         zq.v[i] = 0; zp.v[i] = 0; zg.v[i] = 0;
@@ -219,98 +176,34 @@ __device__ __forceinline__ void stream_piece(StreamArgsK *kargs_p, int q_site, i
         const double *lastp = a.last + ((size_t)k * a.chains + chain) * a.P;
         FORV {
             const int e = lane0 + 64 * i;
-            double q0 = 0.0;
-            if (e < P) {
-                if (a.init_mode == 2) q0 = lastp[e];
-                else if (a.init_mode == 0) {
-                    double u1, u2;
-                    rng_u2(key, 0, K_INIT, (uint32_t)(e >> 1), 0, u1, u2);
-                    q0 = -2.0 + 4.0 * ((e & 1) ? u2 : u1);
-                }
-            }
-            if (resume) {
-                // the sample and the Welford sums of the piece before this one
-                q0 = ck_load(ckp + (0 * NV + i) * 64 + lane0);
-                wmean.v[i] = ck_load(ckp + (1 * NV + i) * 64 + lane0);
-                wm2.v[i] = ck_load(ckp + (2 * NV + i) * 64 + lane0);
-            } else {
-                wmean.v[i] = 0.0; wm2.v[i] = 0.0;
-            }
+            double q0;
+            EPX_INIT_POSITION(q0, e, lastp)
+            if (resume) { EPX_CK_RESTORE_SAMPLE(ckp, lane0, q0); }        // the piece before this one left them
+            else { wmean.v[i] = 0.0; wm2.v[i] = 0.0; }
             zq.v[i] = q0;
             qs.v[i] = q0;
         }
     }
-    const double DELTA = 0.8, GAMMA = 0.05, T0 = 10.0, KAPPA = 0.75, LOG08 = -0.2231435513142097558;
-    double eps = 1.0, da_mu = log(10.0), s_bar = 0, x_bar = 0, da_count = 0;
-    int va_init_buf = 75, va_term = 50, va_base = 25;
-    if (va_init_buf + va_base + va_term > a.warmup && a.warmup >= 20) {
-        va_init_buf = (int)(0.15 * a.warmup);
-        va_term = (int)(0.1 * a.warmup);
-        va_base = a.warmup - (va_init_buf + va_term);
-    }
-    int va_counter = 0, va_wsize = va_base, va_next = va_init_buf + va_base - 1;
-    double va_n = 0;
-    double eps_sum = 0, acc_sum = 0, depth_sum = 0, nleap_tot = 0, ngrad = 0;
-    int ndiv = 0, npost = 0, kept = 0, failed = 0;
-    int t = 0, mode = MODE_INIT, depth = 0, leaf = 0, nleaf = 1, fwd = 1, nleap = 0, divergent = 0, init_try = 0;
-    int ss_trial = 0, ss_dir = 0, ss_after_update = 0;
-    uint32_t ss_t = 0;
-    double H0 = 0, lsw = 0, sum_metro = 0, eps_l = 0;
-    double u_dir = 0.0, gum = 0.0;
-    double dhb = 0.0, lw_m = -INFINITY, lw_s = 0.0;
+#include "nuts_chain_state.inc"
 
-    const bool teacher = a.eps_in != nullptr;
-    if (teacher && active) {
-        eps = a.eps_in[(size_t)sb * a.chains + chain];
-        if (a.inv_e_in) {
-            const double *ie = a.inv_e_in + ((size_t)sb * a.chains + chain) * a.P;
-            FORV { const int e = lane0 + 64 * i; if (e < P) inv_e.v[i] = ie[e]; }
-        }
-    }
-    // opt-in carried adaptation: last call's step size of the chain, the site's pooled sample variances
-    const bool carry = active && !teacher && a.carry_eps != nullptr && a.carry_eps[(size_t)k * a.chains + chain] > 0.0;
-    if (carry) {
-        eps = a.carry_eps[(size_t)k * a.chains + chain];
-        da_mu = log(10.0 * eps);
-        const double *cm = a.carry_metric + (size_t)k * a.P;
-        FORV { const int e = lane0 + 64 * i; if (e < P) inv_e.v[i] = cm[e]; }
-    }
+    EPX_LOAD_TEACHER_CARRY(active, lane0, a.P)
     int finished = active ? 0 : 1;
     double ck_mark = 0.0;                              // (a failed chain's scalars, handed on from boundary to boundary)
     if (resume && active) {
-        FORV inv_e.v[i] = ck_load(ckp + (3 * NV + i) * 64 + lane0);
-        const double ckv = ck_load(ckp + 4 * NV * 64 + lane0);
+        EPX_CK_RESTORE_STATE(ckp, lane0)
         ck_mark = ckv;
-#define EPX_CK_GET(idx, x) ck_assign(x, readlane_d(ckv, idx));
-        EPX_CK_LIST(EPX_CK_GET)
-#undef EPX_CK_GET
         ngrad -= 1.0;                                 // the gradient at the restored sample is evaluated once more
         if (failed) finished = 1;                     // it failed in its first piece, where everything was written
     }
     const bool was_failed = resume && failed != 0;
+
     const uint32_t toff = (uint32_t)a.t_offset + 1u;
 
-    auto flush_dh = [&](int cnt) {
-        const bool ok = lane0 < cnt;
-        const double dh = ok ? dhb : -INFINITY;
-        const double mb = wave_max(dh);
-        const double m_new = fmax(lw_m, mb);
-        double w = 0.0, me = 0.0;
-        if (ok) {
-            w = (m_new == -INFINITY) ? 0.0 : exp(dh - m_new);
-            me = dh > 0 ? 1.0 : exp(dh);
-        }
-        wave_sum2(w, me);
-        const double scale = (lw_m == -INFINITY) ? 0.0 : exp(lw_m - m_new);
-        lw_s = lw_s * scale + w;
-        lw_m = m_new;
-        sum_metro += me;
-    };
+    auto flush_dh = [&](int cnt) { flush_leaf_dh<false>(lane0, cnt, dhb, lw_m, lw_s, sum_metro); };
 
     int counted = is_chain ? 0 : 1;
 #ifdef EPX_STAMPS
-    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tprev = __builtin_amdgcn_s_memtime();
+    STAMP_INIT;                   // (under #ifdef: outside the diagnostic build even its empty statement changes the kernel's code)
 #endif
     for (;;) {
         STAMP(4);
@@ -592,17 +485,7 @@ __device__ __forceinline__ void stream_piece(StreamArgsK *kargs_p, int q_site, i
         if (active && !a.dbg && !was_failed) {
             // checkpoint at the transition boundary: the sample, the Welford sums, the metric and the scalars of
             // EPX_CK_LIST (the gradient at the sample is re-evaluated by the piece that continues)
-            FORV {
-                ck_store(ckp_out + (0 * NV + i) * 64 + lane0, qs.v[i]);
-                ck_store(ckp_out + (1 * NV + i) * 64 + lane0, wmean.v[i]);
-                ck_store(ckp_out + (2 * NV + i) * 64 + lane0, wm2.v[i]);
-                ck_store(ckp_out + (3 * NV + i) * 64 + lane0, inv_e.v[i]);
-            }
-            double ckv = 0.0;
-#define EPX_CK_PUT(idx, x) ckv = lane0 == (idx) ? (double)(x) : ckv;
-            EPX_CK_LIST(EPX_CK_PUT)
-#undef EPX_CK_PUT
-            ck_store(ckp_out + 4 * NV * 64 + lane0, ckv);
+            EPX_CK_SAVE(ckp_out, lane0)
             piece_checkpoint_out();                                 // the record is out before the site is put back
         }
         if (active && !a.dbg && was_failed) { ck_store(ckp_out + 4 * NV * 64 + lane0, ck_mark); piece_checkpoint_out(); }
@@ -610,25 +493,7 @@ __device__ __forceinline__ void stream_piece(StreamArgsK *kargs_p, int q_site, i
         if (threadIdx.x == 0) piece_release(a, smem);
     }
     if (active && !a.dbg && !was_failed && (failed || t >= a.iter)) {
-        double *lastp = a.last + ((size_t)k * a.chains + chain) * a.P;
-        FORV { const int e = lane0 + 64 * i; if (e < a.P) lastp[e] = qs.v[i]; }
-        if (failed) {
-            for (int kk = 0; kk < a.nkeep; ++kk) {
-                double *dst = a.draws + (((size_t)k * a.chains + chain) * a.nkeep + kk) * a.P;
-                FORV { const int e = lane0 + 64 * i; if (e < a.P) dst[e] = qs.v[i]; }
-            }
-        }
-        if (lane0 == 0) {
-            double *st = a.chain_stats + ((size_t)k * a.chains + chain) * ST_COUNT;
-            st[ST_STEPSIZE_MEAN] = a.iter > 0 && !failed ? eps_sum / a.iter : 0.0;
-            st[ST_STEPSIZE_FINAL] = eps;
-            st[ST_NLEAP] = nleap_tot;
-            st[ST_NGRAD] = ngrad;
-            st[ST_NDIV] = ndiv;
-            st[ST_ACCEPT_MEAN] = npost ? acc_sum / npost : 0.0;
-            st[ST_DEPTH_MEAN] = npost ? depth_sum / npost : 0.0;
-            st[ST_FAIL] = failed;
-        }
+        EPX_WRITE_CHAIN_RECORD(lane0, a.P, a.P)
     }
 }
 
@@ -706,7 +571,7 @@ size_t nuts_stream_lds_bytes(int nv, int dpb, int d, int ngmax, int ntmax, int n
 }
 // doubles of global memory per chain: tree stack + cold store
 size_t nuts_stream_chain_doubles(int nv, int max_depth) {
-    return (size_t)max_depth * nuts_stack_record(nv) + (size_t)CV_COUNT * 64 * nv;
+    return (size_t)max_depth * nuts_stack_record(nv) + (size_t)COLD_VECS * 64 * nv;
 }
 
 template <int NV, int DPB, bool RES>
