@@ -835,6 +835,7 @@ static int run_sampler(epx_ctx *c, int k0, int count, const int64_t *seeds, cons
     c->has_last = 1;
     c->last_layout = p.layout;
     c->nsamp = o.chains * nkeep;
+    c->drawn_k0 = k0; c->drawn_count = count;       // the sites whose draws this call leaves behind (epx_named_moments)
     int herr = 0;
     {
         // (no return between a queued copy into this frame and the synchronisation)
@@ -852,6 +853,7 @@ static int run_sampler(epx_ctx *c, int k0, int count, const int64_t *seeds, cons
     }
     if (herr) {
         HIPCHK(hipMemset(c->err_flag, 0, sizeof(int)));
+        c->drawn_count = 0;
         return fail("sampler: a hand-off between the waves of a chain timed out (code %d); the draws of this call are void", herr);
     }
     if (elapsed_ms) {
@@ -1169,6 +1171,63 @@ int epx_mix_sums(epx_ctx *c, double *out) {
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(out, a.out, (size_t)a.len * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int epx_named_len(epx_ctx *c, int k, int name, int *len) {
+    if (!c) return fail("null context");
+    if (!len) return fail("epx_named_len: len is required");
+    if (check_range(c, k, 1)) return -1;
+    const int ng = c->multi ? c->g_cnt[k] : 1;
+    const int n = named_len(name, c->model, c->D, c->d, c->gauss, ng);
+    if (n < 0) return fail("named parameter %d is not defined by this site model", name);
+    *len = n;
+    return 0;
+}
+
+int epx_named_moments(epx_ctx *c, int k0, int count, const int32_t *names, int n_names, const double *theta, int S,
+                      double *mean, double *m2, int *nsamp) {
+    CTX(c);
+    if (check_range(c, k0, count)) return -1;
+    if (!names || n_names < 1 || n_names > EPX_NM_MAX_REQ)
+        return fail("epx_named_moments: between 1 and %d names", (int)EPX_NM_MAX_REQ);
+    if (!mean || !m2) return fail("epx_named_moments: mean and m2 are required");
+    NamedArgs a;
+    a.model = c->model; a.D = c->D; a.d = c->d; a.gauss = c->gauss; a.P = c->P;
+    a.ng_max = c->ng_max; a.k0 = k0; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    a.n_names = n_names; a.off[0] = 0;
+    for (int i = 0; i < n_names; ++i) {
+        const int n = named_len(names[i], a.model, a.D, a.d, a.gauss, a.ng_max);
+        if (n < 0) return fail("named parameter %d is not defined by this site model", (int)names[i]);
+        a.name[i] = names[i]; a.off[i + 1] = a.off[i] + n;
+    }
+    for (int i = n_names; i < EPX_NM_MAX_REQ; ++i) { a.name[i] = 0; a.off[i + 1] = a.off[n_names]; }
+    a.L = a.off[n_names];
+    const size_t P = c->P;
+    if (theta) {
+        if (S < 1) return fail("epx_named_moments: S = %d draws", S);
+        const size_t need = (size_t)count * S * P;
+        HIPCHK(c->inj.grow(need));
+        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
+        a.draws = c->inj;
+    } else {
+        S = c->s_chains * c->s_nkeep;
+        if (!c->draws || S < 1 || c->drawn_count < 1) return fail("no draws yet");
+        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
+            return fail("epx_named_moments: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only",
+                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
+        a.draws = c->draws + (size_t)k0 * S * P;
+    }
+    a.S = S;
+    const size_t nout = (size_t)count * a.L;
+    HIPCHK(c->named_out.grow(2 * nout));
+    a.mean = c->named_out; a.m2 = c->named_out + nout;
+    hipLaunchKernelGGL(k_named_moments, dim3(count), dim3(256), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(mean, a.mean, nout * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(m2, a.m2, nout * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (nsamp) *nsamp = S;
     return 0;
 }
 

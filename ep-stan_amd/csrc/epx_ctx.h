@@ -95,12 +95,14 @@ struct epx_ctx {
     DevBuf<double> dense_ws;        // global workspace for dense kernels (lazily sized)
     // sampler buffers (lazily sized)
     int s_chains = 0, s_nkeep = 0;
+    int drawn_k0 = 0, drawn_count = 0;   // sites the last sampling call covered: whose block of `draws` is current
     DevBuf<double> draws, last, chain_stats, site_stats, stack;
     DevBuf<double> team_passes;     // K: row-team passes of the last sampling call per site (layout 7; 0 elsewhere)
     DevBuf<int64_t> seeds_d;
     DevBuf<double> dbg;             // [1+P] lp, grad ; [P] theta (test hook)
     DevBuf<int64_t> dbg_seed;
     DevBuf<double> inj;             // injected samples (test hook)
+    DevBuf<double> named_out;       // epx_named_moments: [mean | M2] records of the call
     int has_last = 0;
     int nsamp = 0;                  // draws per site of the last tilted/moments call
     double last_df = 0.0;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/epx.h"
+
 namespace epx {
 
 // Where a dense kernel keeps its two d x ld work matrices + 4 vectors.
@@ -81,6 +83,39 @@ struct ForceArgs {
     uint8_t *forced;
     double *min_eig;
 };
+
+// Named parameters of the site models from the sampled coordinates theta = [phi | eta (ng) | etb (ng x D)]
+// (site_params.py restates the Stan programs; Master.mix_pred, method.py:1304-1478): elements of `name` (enum
+// epx_named) at a site with ng groups, its per-site shape flattened in C order; -1: the model does not define it.
+// model = the b-model id, d = dphi (the Gaussian family's leading log sigma included).
+__host__ __device__ inline int named_len(int name, int model, int D, int d, int gauss, int ng) {
+    const bool etb = model != EPX_M1B_SG;
+    switch (name) {
+    case EPX_NM_PHI: return d;
+    case EPX_NM_ETA: case EPX_NM_ALPHA: return ng;
+    case EPX_NM_BETA: return etb ? ng * D : D;
+    case EPX_NM_SIGMA_A: return 1;
+    case EPX_NM_ETB: return etb ? ng * D : -1;
+    case EPX_NM_SIGMA_B: return !etb ? -1 : model == EPX_M2B_SG ? 1 : D;
+    case EPX_NM_MU_A: return model >= EPX_M4B_SG ? 1 : -1;
+    case EPX_NM_MU_B: return model >= EPX_M4B_SG ? D : -1;
+    case EPX_NM_SIGMA: return gauss ? 1 : -1;
+    default: return -1;
+    }
+}
+
+enum { EPX_NM_MAX_REQ = 16 };          // names one call may ask for
+struct NamedArgs {
+    int model, D, d, gauss, P, S;
+    int ng_max;                        // groups of the context's largest site: sizes the output row
+    int k0;                            // first site (absolute: indexes site_g0)
+    const int *site_g0;                // prefix sums of the groups per site, or NULL: one group everywhere
+    const double *draws;               // site b of the call at draws + b * S * P: (S, P) row-major, chain-major
+    int n_names, L;                    // requested names; L = off[n_names] elements per output row
+    int name[EPX_NM_MAX_REQ], off[EPX_NM_MAX_REQ + 1];      // off: first element of each name's block (lengths at ng_max)
+    double *mean, *m2;                 // count x L each
+};
+__global__ void k_named_moments(NamedArgs a);
 
 __global__ void k_cavity(CavityArgs a);
 __global__ void k_moments(MomentArgs a);

@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from . import site_params as _site_params
 from ._lib import SamplerOpts, check, dptr
 
 MODEL_IDS = {'m1b_sg': 0, 'm2b_sg': 1, 'm3b_sg': 2, 'm4b_sg': 3, 'm5b_sg': 4,
@@ -463,6 +464,52 @@ class HipEngine(object):
         out = np.zeros(2 * self.d * self.d + self.d)
         check(self.lib.epx_mix_sums(self.ctx, dptr(out)))
         return out
+
+    def named_moments(self, names, k0=0, count=None, theta=None):
+        """Per-site moments of named parameters of the site model (epx_named_moments, include/epx.h): (n, mean, m2)
+        with n the draws per site and mean / m2 lists, one entry per site, of {name: ndarray} -- the mean and the
+        centred sum of squares in the per-site shapes of site_params.named_draws.  The draws are those of the last
+        sampling call, on the device; `theta` (count, S, P) injects draws instead (test hook)."""
+        count = self.K - k0 if count is None else count
+        names = [names] if isinstance(names, str) else list(names)
+        for name in names:
+            if name not in _site_params.NAME_IDS:
+                raise ValueError('unknown parameter name {!r} (known: {})'.format(name, sorted(_site_params.NAME_IDS)))
+        ids = np.array([_site_params.NAME_IDS[name] for name in names], dtype=np.int32)
+        mid, gauss, sg = MODEL_IDS[self.model] % 5, is_gauss(self.model), self.model.endswith('_sg')
+        ng_max = 1 if self.g_cnt is None else int(self.g_cnt.max())
+        S = 0
+        if theta is not None:
+            theta = np.ascontiguousarray(theta, dtype=np.float64)
+            if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
+                raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
+            S = theta.shape[1]
+        # the widest site's lengths size a row; an undefined name fails in the library like any other error
+        lens = []
+        for i in ids:
+            n = ctypes.c_int()
+            check(self.lib.epx_named_len(self.ctx, int(np.argmax(self.g_cnt)) if self.g_cnt is not None else 0, int(i),
+                                         ctypes.byref(n)))
+            lens.append(n.value)
+        L = int(sum(lens))
+        mean = np.zeros((count, L))
+        m2 = np.zeros((count, L))
+        n = ctypes.c_int()
+        check(self.lib.epx_named_moments(self.ctx, int(k0), int(count), ids.ctypes.data_as(_lib.c_int32_p), len(names),
+                                         dptr(theta), int(S), dptr(mean), dptr(m2), ctypes.byref(n)))
+        off = np.concatenate(([0], np.cumsum(lens)))
+        means, m2s = [], []
+        for b in range(count):
+            ng = 1 if self.g_cnt is None else int(self.g_cnt[k0 + b])
+            dm, dv = {}, {}
+            for j, name in enumerate(names):
+                shape = _site_params.named_shape(mid, self.D, ng, gauss, sg, name)
+                size = int(np.prod(shape, dtype=np.int64))
+                dm[name] = mean[b, off[j]:off[j] + size].reshape(shape).copy()
+                dv[name] = m2[b, off[j]:off[j] + size].reshape(shape).copy()
+            means.append(dm)
+            m2s.append(dv)
+        return n.value, means, m2s
 
     def accept(self, df):
         check(self.lib.epx_accept(self.ctx, float(df)))

@@ -5,6 +5,9 @@ iteration count, `main(model_name, conf)` for `run_ep` with K == J (one group
 per site, the `_sg` densities), the result `.npz` schema
 (`m_s_ep, S_s_ep, time_s_ep, mstepsize_s_ep, mrhat_s_ep, othertimes`) with the
 initial approximation prepended, and `kl_mvn` (plot_res.py:41-60) to score it.
+With `conf.mix` the final approximation is mixed from the last samples of all
+sites (`mix_phi`) and the group-level `alpha` / `beta` moments are stored as
+`m_<name>_ep` / `v_<name>_ep` (`mix_pred` with `_create_pmaps`, fit.py:408-421).
 The competing methods of fit.py (full model, consensus MC, target run) need
 Stan itself and are out of scope; asking for them raises NotImplementedError.
 """
@@ -74,6 +77,46 @@ def kl_mvn(m0, S0, m1, S1):
     return 0.5 * (np.trace(Q1.dot(S0)) + dm.dot(Q1.dot(dm)) - d) - 0.5 * ld0 + 0.5 * ld1
 
 
+def _site_param_definitions(model, model_name, J, K):
+    """The model's `get_param_definitions()` as the SITES of this package hold the parameters.  They differ from the
+    reference's in one place: with several groups per site (K < J) the multi-group densities of m2b / m2a here carry
+    one `etb` block per GROUP (the layout [phi | eta (groups) | etb (groups x D)] of every model with an `etb` block,
+    site_params.py), so a site's `beta = etb * sigma_b` is (groups, D) and belongs to its groups -- where the reference's
+    m2b.stan has one `vector[D] etb` per site and calls `beta` (D,), shared.  Mixed as a shared (D,) vector those records
+    would pool unrelated groups by position; they are mixed per group, as m3b's are."""
+    names, shapes, hiers = model.get_param_definitions()
+    if K < J and model_name in ('m2b', 'm2a'):
+        i = names.index('beta')
+        shapes = shapes[:i] + ((J, model.D),) + shapes[i + 1:]
+        hiers = hiers[:i] + (0,) + hiers[i + 1:]
+    return names, shapes, hiers
+
+
+def _create_pmaps(phiers, J, K, Ns):
+    """Per parameter, the map from every site's elements to the indexes of the full model's parameter
+    (fit.py:763-849), as `Master.mix_pred` takes it: None for a parameter all groups share, otherwise one
+    NumPy index per site along the parameter's group dimension `ih` -- the site's block of `Ns[k]` groups when a
+    site holds several (K < J), the site's number when it holds one (K == J)."""
+    if K < 2:
+        raise ValueError("K should be at least 2.")
+    if K > J:
+        raise NotImplementedError("Splitting the groups not implemented.")
+    if K < J:
+        starts = np.concatenate(([0], np.cumsum(np.asarray(Ns, dtype=np.int64))))
+        picks = [slice(int(starts[k]), int(starts[k + 1])) for k in range(K)]
+    else:
+        picks = list(range(K))
+    pmaps = []
+    for ih in phiers:
+        if ih is None:
+            pmaps.append(None)
+        elif ih == 0:
+            pmaps.append(list(picks) if K < J else np.arange(K))
+        else:
+            pmaps.append([(slice(None),) * ih + (pick,) for pick in picks])
+    return pmaps
+
+
 def main(model_name, conf, ret_master=False, verbose=True, _engine_factory=None, **master_kwargs):
     """The `run_ep` branch of fit.py:210-459 for K == J.
 
@@ -94,6 +137,7 @@ def main(model_name, conf, ret_master=False, verbose=True, _engine_factory=None,
         data = model.simulate_data(rng=conf.seed_data)
     S0, m0, Q0, r0 = model.get_prior()
     prior = {'Q': Q0, 'r': r0}
+    pnames, pshapes, phiers = _site_param_definitions(model, model_name, J, K)          # fit.py:252
     iters_to_run = EP_DEFAULT_ITERS_TO_RUN(K) if conf.iter is None else conf.iter      # fit.py:284-287
     df0 = default_df0(K) if conf.damp is None else conf.damp                             # fit.py:289-293
     epstan_options = dict(prior=prior, prec_estim=conf.prec_estim, df0=df0, init_site=None,
@@ -107,11 +151,13 @@ def main(model_name, conf, ret_master=False, verbose=True, _engine_factory=None,
     if K < J:
         # several groups per site (fit.py:310-324): the multi-group program m*b.stan
         Nk, Nj_k, j_ind_k = distribute_groups(J, K, data.Nj)
+        pmaps = _create_pmaps(phiers, J, K, Nj_k)                                        # fit.py:324
         epstan_master = Master(model_name, data.X, data.y, A_k={'J': Nj_k}, A_n={'j_ind': j_ind_k + 1},
                                site_sizes=Nk, **epstan_options, **master_kwargs)
     else:
         epstan_master = Master(model.site_model, data.X, data.y, site_sizes=data.Nj,
                                **epstan_options, **master_kwargs)                        # fit.py:326-335
+        pmaps = _create_pmaps(phiers, J, K, None)                                        # fit.py:337
     if ret_master:
         return epstan_master
     S_ep_init, m_ep_init = epstan_master.cur_approx()                                    # fit.py:351
@@ -128,11 +174,15 @@ def main(model_name, conf, ret_master=False, verbose=True, _engine_factory=None,
     if info:
         res['last_iter'] = epstan_master.iter                                            # fit.py:391-403
     elif conf.mix:
-        # fit.py:408-411, 440-441: the final approximation from the last samples of all the sites.  `mix_pred`
-        # (fit.py:414-421) reads worker.fit, which the reference's own child-process sampler never keeps: out of scope
+        # fit.py:408-421, 440-442: the final approximation from the last samples of all the sites, and the mean and
+        # variance of the model's inferred parameters (per-site moments from the draws on the device, Master.mix_pred)
         S_ep, m_ep = epstan_master.mix_phi()
         res['m_phi_ep'] = m_ep
         res['S_phi_ep'] = S_ep
+        pms, pvars = epstan_master.mix_pred(pnames, pmaps, pshapes)
+        for pname, pm, pv in zip(pnames, pms, pvars):
+            res['m_' + pname + '_ep'] = pm
+            res['v_' + pname + '_ep'] = pv
     if conf.save_res:
         os.makedirs(RES_PATH, exist_ok=True)
         fname = 'res_d_{}_{}.npz'.format(model_name, conf.id) if conf.id else 'res_d_{}.npz'.format(model_name)

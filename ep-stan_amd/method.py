@@ -31,6 +31,7 @@ from numpy.linalg import LinAlgError
 
 from . import dist as _dist
 from . import engine as _engine
+from . import mix_pred as _mix_pred
 from . import site_params as _site_params
 from .seeds import MAX_UINT, run_seeds, stan_seed, stan_seeds
 from .util import invert_normal_params
@@ -226,6 +227,7 @@ class Worker(object):
         if self.Q is not None:
             self._eng.set_global(self.Q, self.r)      # dQi -= Q, dri -= r use the aliased arrays (:457-458)
         if injector is not None:
+            m._draws_injected = True          # (mix_pred: injected draws hold phi only)
             self._refresh_for_injection()
             samp = np.asfortranarray(injector(self.data, self.stan_params))
             ok = bool(self._eng.moments_batch(samp[:, :, None], self._cur_estim(),
@@ -462,6 +464,7 @@ class Master(object):
         self.adapt = gpu['adapt']
         self.comm = gpu['comm'] if gpu['comm'] is not None else _dist.LocalComm()
         self._sample_injector = None        # test hook: f(data, stan_params) -> (S, d) draws
+        self._draws_injected = False        # the last iteration's draws came from the injector (phi only)
         self.last_site_stats = None         # sampler statistics of the last iteration (local sites)
         self.sampling_ms = []               # device time of every sampling launch (this rank)
         self.ngrad_log = []                 # gradient evaluations of every sampling launch (this rank)
@@ -504,10 +507,12 @@ class Master(object):
         r0w, r1w = int(self.k_lim[self.k_lo]), int(self.k_lim[self.k_hi])
         k_lim_local = np.asarray(self.k_lim[self.k_lo:self.k_hi + 1], dtype=np.int64) - r0w
         groups = {}
+        self._site_ng = np.ones(self.K, dtype=np.int64)        # groups per site (all sites: mix_pred's record shapes)
         if not self.model_name.endswith('_sg'):
             # several groups per site (K < J, fit.py:310-324): the multi-group programs take the
             # number of groups `J` per site (A_k) and the 1-based group index `j_ind` per row (A_n)
             g_cnt, g_lim = self._site_groups()
+            self._site_ng = np.asarray(g_cnt, dtype=np.int64)
             glo = int(np.sum(g_cnt[:self.k_lo]))
             ghi = glo + int(np.sum(g_cnt[self.k_lo:self.k_hi]))
             groups = dict(g_cnt=g_cnt[self.k_lo:self.k_hi], g_lim=g_lim[glo:ghi + 1] - r0w)
@@ -640,6 +645,89 @@ class Master(object):
         out_S[...] = S
         out_m[...] = m
         return out_S, out_m
+
+    def _site_spec(self):
+        """(b-model id, Gaussian family, single-group program) of the site model, as site_params takes them."""
+        name = self.model_name
+        return _engine.MODEL_IDS[name] % 5, _engine.is_gauss(name), name.endswith('_sg')
+
+    def _local_named_moments(self, names):
+        """(n, mean, m2) of the named parameters for this rank's sites: lists of {name: ndarray} (see
+        HipEngine.named_moments).  The device engine computes them next to the draws; an engine without
+        `named_moments` (the CPU oracle the tests inject) hands its draws to site_params.named_moments_host."""
+        eng = self.engine
+        if hasattr(eng, 'named_moments'):
+            return eng.named_moments(names)
+        mid, gauss, sg = self._site_spec()
+        n, means, m2s = 0, [], []
+        for j in range(self.K_local):
+            theta = eng.get_draws(j, all_params=True)
+            n, m, v = _site_params.named_moments_host(mid, self.D, int(self._site_ng[self.k_lo + j]), gauss, sg,
+                                                      theta, names)
+            means.append(m)
+            m2s.append(v)
+        return n, means, m2s
+
+    def _gather_named(self, names, n, means, m2s):
+        """Per-site records of ALL sites on every rank: ns (K), and lists of {name: ndarray}.  One record per site,
+        [n | means | M2s] flattened and padded to the widest site, gathered like the site arrays."""
+        K = self.K
+        if self.comm.world == 1:
+            return np.full(K, n, dtype=np.int64), means, m2s
+        mid, gauss, sg = self._site_spec()
+        shapes = [[_site_params.named_shape(mid, self.D, int(self._site_ng[k]), gauss, sg, name) for name in names]
+                  for k in range(K)]
+        sizes = [[int(np.prod(sh, dtype=np.int64)) for sh in row] for row in shapes]
+        W = max(sum(row) for row in sizes)
+        rec = np.zeros((2 * W + 1, self.K_local), order='F')
+        rec[0, :] = n
+        for j in range(self.K_local):
+            rec[1:1 + sum(sizes[self.k_lo + j]), j] = np.concatenate([np.ravel(means[j][name]) for name in names])
+            rec[1 + W:1 + W + sum(sizes[self.k_lo + j]), j] = np.concatenate([np.ravel(m2s[j][name]) for name in names])
+        full = self.comm.allgather_sites(rec, K)
+        ms, vs = [], []
+        for k in range(K):
+            dm, dv, at = {}, {}, 0
+            for name, sh, size in zip(names, shapes[k], sizes[k]):
+                dm[name] = full[1 + at:1 + at + size, k].reshape(sh)
+                dv[name] = full[1 + W + at:1 + W + at + size, k].reshape(sh)
+                at += size
+            ms.append(dm)
+            vs.append(dv)
+        return np.rint(full[0, :]).astype(np.int64), ms, vs
+
+    def mix_pred(self, params, smap=None, param_shapes=None):
+        """Mean and variance of named parameters of the site model from the tilted draws of the last iteration
+        (method.py:1304-1478; experiment/fit.py:408-421 calls it for the models' `alpha`, `beta`).
+
+        params: a name or a list of names; smap: per parameter None (every site holds the whole parameter) or, per
+        site, the NumPy index of the site's elements in the global parameter (fit._create_pmaps); param_shapes: the
+        global shapes, needed with smap.  Returns (mean, var), lists when `params` is a list.
+
+        The reference extracts every draw of every worker's kept `fit`; here the draws are still in device memory,
+        the kernel k_named_moments reduces them to per-site (mean, centred sum of squares) records, and only those
+        are combined on the host (mix_pred.combine_moments) -- no `save_last_param` needed.  With several ranks the
+        records are gathered over the communicator; every rank returns the same result."""
+        if self.iter == 0:
+            raise RuntimeError("Can not mix samples before at least one iteration has been done.")
+        if self._draws_injected:
+            raise RuntimeError("The draws of the last iteration were injected (`_sample_injector`): they hold phi "
+                               "only, named parameters can not be mixed.")
+        only_one_param = isinstance(params, str)
+        if only_one_param:
+            params, smap, param_shapes = [params], [smap], [param_shapes]
+        params = list(params)
+        ns, ms, vs = self._gather_named(params, *self._local_named_moments(params))
+        mean, var = [], []
+        for ip, par in enumerate(params):
+            m, v = _mix_pred.combine_moments(
+                ns, [rec[par] for rec in ms], [rec[par] for rec in vs],
+                smap[ip] if smap is not None else None, param_shapes[ip] if param_shapes is not None else None)
+            mean.append(m)
+            var.append(v)
+        if only_one_param:
+            return mean[0], var[0]
+        return mean, var
 
     # a site whose slowest chain took more than this fraction of the iteration's slowest chain is
     # scheduled one workgroup per chain next time (measured leapfrog: 5.6 vs 10.3 us at D=32, n=500)
@@ -790,6 +878,7 @@ class Master(object):
                     raise RuntimeError('Cavity has to be calculated before tilted.')
             sseeds = stan_seeds(seeds[cur_iter, lo:hi])             # :342-346
             estim = w0._cur_estim()
+            self._draws_injected = self._sample_injector is not None
             if self._sample_injector is not None:
                 posdefs_l, tl, ml, rl = self._tilted_injected(sseeds, estim)
             else:

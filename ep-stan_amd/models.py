@@ -131,6 +131,17 @@ def _regulate_rows(rng, beta_j, redraw):
             beta_sum += beta_j[j, index]
 
 
+def _param_definitions(J, D, beta_per_group, gauss):
+    """(names, shapes, hiers) of the inferred parameters (the models' get_param_definitions, e.g. m4b.py:220-239):
+    the shape of each in the full model and the index of its group dimension (None: shared by the groups)."""
+    names = ('alpha', 'beta')
+    shapes = ((J,), (J, D) if beta_per_group else (D,))
+    hiers = (0, 0 if beta_per_group else None)
+    if gauss:
+        names, shapes, hiers = names + ('sigma',), shapes + ((),), hiers + (None,)
+    return names, shapes, hiers
+
+
 class _LogisticBase(object):
     """Shared skeleton of the remaining logistic simulators: the model-specific part draws the
     parameters (in the reference's order of random draws) and returns (alpha_j, beta or beta_j,
@@ -161,6 +172,11 @@ class _LogisticBase(object):
         m0 = np.zeros(self.dphi)
         return np.diag(v).T, m0, np.diag(1/v).T, m0/v
 
+    BETA_PER_GROUP = True           # `vector[D] beta[J]`; False: one `vector[D] beta` for all groups
+
+    def get_param_definitions(self):
+        return _param_definitions(self.J, self.D, self.BETA_PER_GROUP, False)
+
 
 class m1b(_LogisticBase):
     """y ~ bernoulli_logit(alpha_j + x beta), alpha_j ~ N(0, sigma_a), beta shared by the groups,
@@ -170,6 +186,7 @@ class m1b(_LogisticBase):
     SIGMA_B = 1.0
     M0_A, V0_A, M0_B, V0_B = 0, 1.5**2, 0, 1.5**2     # m1b.py:46-50
     site_model = 'm1b_sg'
+    BETA_PER_GROUP = False
 
     def _dphi(self, D):
         return D + 1
@@ -224,6 +241,7 @@ class m2b(_LogisticBase):
     (models/m2b.py; density m2b_sg.stan)."""
     SIGMA_A, SIGMA_B = 1, 1                            # m2b.py:38-42
     site_model = 'm2b_sg'
+    BETA_PER_GROUP = False
 
     def _dphi(self, D):
         return 2
@@ -328,6 +346,9 @@ class m1a(object):
         m0 = np.zeros(self.dphi)
         return np.diag(v).T, m0, np.diag(1/v).T, m0/v
 
+    def get_param_definitions(self):
+        return _param_definitions(self.J, self.D, False, True)
+
 
 class m4a(object):
     """y ~ N(alpha_j + x beta_j, sigma), alpha_j ~ N(mu_a, sigma_a), beta_jd ~ N(mu_b_d, sigma_b_d),
@@ -373,6 +394,9 @@ class m4a(object):
         m0 = np.zeros(self.dphi)
         return np.diag(v).T, m0, np.diag(1/v).T, m0/v
 
+    def get_param_definitions(self):
+        return _param_definitions(self.J, self.D, True, True)
+
 
 class _GaussBase(object):
     """Shared skeleton of the remaining linear-regression simulators (noise sigma = 1, all prior
@@ -411,12 +435,18 @@ class _GaussBase(object):
         m0 = np.zeros(self.dphi)
         return np.diag(v).T, m0, np.diag(1/v).T, m0/v
 
+    BETA_PER_GROUP = True
+
+    def get_param_definitions(self):
+        return _param_definitions(self.J, self.D, self.BETA_PER_GROUP, True)
+
 
 class m2a(_GaussBase):
     """phi = [log sigma, log sigma_a, log sigma_b], beta ~ N(0, sigma_b) shared (models/m2a.py; density
     m2a_sg.stan).  The reference's simulator names its generator `rnd_data` but receives it as
     `rng` (m2a.py:91-174) and raises NameError; this is the evident intent."""
     site_model = 'm2a_sg'
+    BETA_PER_GROUP = False
 
     def _dphi(self, D):
         return 3

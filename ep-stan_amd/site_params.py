@@ -13,6 +13,10 @@ PyStan's random permutation.
 
 import numpy as np
 
+# enum epx_named (include/epx.h)
+NAME_IDS = {'phi': 0, 'eta': 1, 'alpha': 2, 'beta': 3, 'sigma_a': 4, 'etb': 5, 'sigma_b': 6, 'mu_a': 7, 'mu_b': 8,
+            'sigma': 9}
+
 # sampled blocks behind phi, per b-model id: does the program have the `etb` block?
 _HAS_ETB = {0: False, 1: True, 2: True, 3: True, 4: True}
 
@@ -88,3 +92,34 @@ def named_draws(model_id, D, ng, gauss, single_group, theta, wanted):
             v = v[:, 0, :]
         out[name] = v
     return out
+
+
+def named_shape(model_id, D, ng, gauss, single_group, name):
+    """Per-site shape of `name` -- the shape `named_draws` returns behind the draw axis."""
+    o, d, _, _ = layout(model_id, D, ng, gauss)
+    if name not in names(model_id, gauss):
+        raise ValueError("parameter {!r} is not defined by this site model (known: {})"
+                         .format(name, sorted(names(model_id, gauss))))
+    per_group = {'eta': (), 'alpha': (), 'etb': (D,), 'beta': (D,)}
+    if name == 'beta' and model_id == 0:
+        return (D,)
+    if name in per_group:
+        return per_group[name] if single_group else (ng,) + per_group[name]
+    if name == 'phi':
+        return (d,)
+    if name == 'mu_b' or (name == 'sigma_b' and model_id != 1):
+        return (D,)
+    return ()
+
+
+def named_moments_host(model_id, D, ng, gauss, single_group, theta, wanted):
+    """(n, mean, m2) of the named parameters of ONE site from its draws theta (S, P) with NumPy:
+    mean[name] and the centred sum of squares m2[name] = sum_s (x_s - mean)^2 in the per-site shapes of
+    `named_draws`.  What the device kernel k_named_moments (csrc/named_moments.hip) computes; the
+    expectation of its tests, and `Master.mix_pred`'s route on an engine without `named_moments`."""
+    draws = named_draws(model_id, D, ng, gauss, single_group, theta, wanted)
+    mean, m2 = {}, {}
+    for name, x in draws.items():
+        mean[name] = x.mean(axis=0)
+        m2[name] = np.square(x - mean[name]).sum(axis=0)
+    return np.asarray(theta).shape[0], mean, m2

@@ -255,6 +255,27 @@ int epx_nuts_transitions(epx_ctx *ctx, int k0, int count, const int64_t *seeds, 
  * context's sites, from the tilted moments of the last epx_tilted_batch / epx_moments_batch. */
 int epx_mix_sums(epx_ctx *ctx, double *out);
 
+/* Named parameters of the site models for Master.mix_pred (method.py:1304-1478, called by experiment/fit.py:408-421 with
+ * the models' inferred parameters `alpha`, `beta`): the reference walks `worker.fit.extract(pars=par)` of every worker on
+ * the host; here the draws of every sampled coordinate theta = [phi | eta (groups) | etb (groups x D)] are still in device
+ * memory when a sampling call returns, and the `parameters` / `transformed parameters` of
+ * experiment/models/m{1..5}{a,b}[_sg].stan are applied to them there:
+ *   phi eta etb mu_a mu_b: coordinates;  sigma_a sigma_b sigma: exp of their logarithms in phi;
+ *   alpha = [mu_a +] eta sigma_a;  beta = [mu_b +] etb sigma_b (element-wise), m1b: phi's `beta` slice. */
+enum epx_named { EPX_NM_PHI = 0, EPX_NM_ETA, EPX_NM_ALPHA, EPX_NM_BETA, EPX_NM_SIGMA_A, EPX_NM_ETB, EPX_NM_SIGMA_B,
+                 EPX_NM_MU_A, EPX_NM_MU_B, EPX_NM_SIGMA, EPX_NM_COUNT };
+/* elements of `name` at site k (its per-site shape flattened in C order: (ng,), (ng, D), (D,), (d,), scalars 1);
+ * error if the context's model does not define the name */
+int epx_named_len(epx_ctx *ctx, int k, int name, int *len);
+/* Per site and element the mean and the CENTRED sum of squares M2 = sum_s (x_s - mean)^2 over the site's draws (two
+ * passes; what method.py:1390-1395 / :1426-1430 compute per worker): mean[count * L], m2[count * L], L = sum over the
+ * names of the length at the context's LARGEST site; row = site, names in the order given (at most 16), zero behind a
+ * site's own elements.  theta == NULL: the draws of the last sampling call (error "no draws yet" before one, and an
+ * error when that call did not cover every site of the range: their draws would be stale), S is ignored; otherwise TEST HOOK: injected draws (count, S, P) row-major, P = the context's record stride (a site reads
+ * its own coordinates of a row only).  nsamp out (may be NULL): draws per site.  One launch, one synchronisation. */
+int epx_named_moments(epx_ctx *ctx, int k0, int count, const int32_t *names, int n_names,
+                      const double *theta, int S, double *mean, double *m2, int *nsamp);
+
 /* ---------------------------------------------------------------------------------------------
  * Several GPUs: sites are sharded over the ranks (one context each); the only exchange of an EP
  * iteration is the reduction of method.py:1073-1074 (Q = sum_k Qi2 + Q0 over ALL sites) and the logical
