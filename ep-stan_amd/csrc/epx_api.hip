@@ -1231,6 +1231,56 @@ int epx_named_moments(epx_ctx *c, int k0, int count, const int32_t *names, int n
     return 0;
 }
 
+int epx_pooled_moments(epx_ctx *c, int k0, int count, const double *center, const double *theta, int S, int want_scatter,
+                       double *sum, double *scatter, long long *n) {
+    CTX(c);
+    if (check_range(c, k0, count)) return -1;
+    if (!sum || !n) return fail("epx_pooled_moments: sum and n are required");
+    if (want_scatter && !scatter) return fail("epx_pooled_moments: want_scatter without a scatter array");
+    const size_t P = c->P, d = c->d;
+    PooledArgs a;
+    if (theta) {
+        if (S < 1) return fail("epx_pooled_moments: S = %d draws", S);
+        const size_t need = (size_t)count * S * P;
+        HIPCHK(c->inj.grow(need));
+        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
+        a.draws = c->inj;
+    } else {
+        S = c->s_chains * c->s_nkeep;
+        if (!c->draws || S < 1 || c->drawn_count < 1) return fail("no draws yet");
+        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
+            return fail("epx_pooled_moments: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only",
+                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
+        a.draws = c->draws + (size_t)k0 * S * P;
+    }
+    a.d = c->d; a.P = c->P; a.nt = (c->d + 15) / 16; a.want_scatter = want_scatter ? 1 : 0;
+    a.n = (long long)count * S;
+    // the slabs depend on (n, d) alone: the same partition, hence the same bits, on every call.  About 2048 workgroups
+    // (eight per compute unit) of at least 128 records each; whole groups of 16 records (four per wave and step)
+    const int pairs = want_scatter ? a.nt * (a.nt + 1) / 2 : a.nt;
+    const long long max_slabs = 2048 / pairs > 1 ? 2048 / pairs : 1;
+    a.slab_rows = (a.n + max_slabs - 1) / max_slabs;
+    if (a.slab_rows < 128) a.slab_rows = 128;
+    a.slab_rows = (a.slab_rows + 15) / 16 * 16;
+    a.nslab = (int)((a.n + a.slab_rows - 1) / a.slab_rows);
+    const size_t n_ps = want_scatter ? (size_t)a.nslab * pairs * 256 : 0, n_pm = (size_t)a.nslab * a.nt * 16;
+    HIPCHK(c->pooled_ws.grow(n_ps + n_pm + d * d + 2 * d));
+    a.part_scatter = c->pooled_ws; a.part_sum = a.part_scatter + n_ps;
+    a.out_scatter = a.part_sum + n_pm; a.out_sum = a.out_scatter + d * d;
+    double *center_d = a.out_sum + d;
+    if (center) HIPCHK(hipMemcpyAsync(center_d, center, d * 8, hipMemcpyHostToDevice, c->stream));
+    a.center = center ? center_d : nullptr;
+    hipLaunchKernelGGL(k_pooled_partial, dim3(pairs, a.nslab), dim3(256), 0, c->stream, a);
+    const int nout = (int)((want_scatter ? d * d : 0) + d);
+    hipLaunchKernelGGL(k_pooled_final, dim3((nout + 255) / 256), dim3(256), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sum, a.out_sum, d * 8, hipMemcpyDeviceToHost, c->stream));
+    if (want_scatter) HIPCHK(hipMemcpyAsync(scatter, a.out_scatter, d * d * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n = a.n;
+    return 0;
+}
+
 static int launch_global(epx_ctx *c, const double *packed_dev, double df, int want_moments,
                          const double *tgt = nullptr, double *crit = nullptr) {
     GlobalArgs a;

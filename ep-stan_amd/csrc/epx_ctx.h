@@ -103,6 +103,7 @@ struct epx_ctx {
     DevBuf<int64_t> dbg_seed;
     DevBuf<double> inj;             // injected samples (test hook)
     DevBuf<double> named_out;       // epx_named_moments: [mean | M2] records of the call
+    DevBuf<double> pooled_ws;       // epx_pooled_moments: [partial tiles | partial sums | scatter | sum | centre]
     int has_last = 0;
     int nsamp = 0;                  // draws per site of the last tilted/moments call
     double last_df = 0.0;

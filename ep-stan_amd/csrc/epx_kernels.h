@@ -117,6 +117,21 @@ struct NamedArgs {
 };
 __global__ void k_named_moments(NamedArgs a);
 
+// Pooled moments of the first d coordinates of n = sites x draws records (pooled_moments.hip; experiment/fit.py:639-646).
+struct PooledArgs {
+    int d, P, nt;                      // nt = ceil(d / 16) column tiles
+    int want_scatter;                  // 0: the sums alone (diagonal tile pairs only, no matrix pipe)
+    long long n, slab_rows;            // records; records per slab
+    int nslab;
+    const double *draws;               // (n, P) row-major
+    const double *center;              // d, or NULL = 0
+    double *part_scatter;              // nslab x pairs x 256: a pair's tile in the accumulator's element order
+    double *part_sum;                  // nslab x nt x 16
+    double *out_scatter, *out_sum;     // d x d column-major, d
+};
+__global__ void k_pooled_partial(PooledArgs a);
+__global__ void k_pooled_final(PooledArgs a);
+
 __global__ void k_cavity(CavityArgs a);
 __global__ void k_moments(MomentArgs a);
 __global__ void k_site_sums_partial(SumArgs a);

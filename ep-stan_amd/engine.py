@@ -511,6 +511,30 @@ class HipEngine(object):
             m2s.append(dv)
         return n.value, means, m2s
 
+    def pooled_moments(self, center=None, k0=0, count=None, theta=None, want_scatter=True):
+        """Moments of the phi draws of the sites k0..k0+count pooled (epx_pooled_moments, include/epx.h): (n, sum, scatter)
+        with n the number of draws, sum (d) = sum (x - center) and scatter (d, d) = sum (x - center)(x - center)', None
+        without `want_scatter`; `center` None = 0.  The draws are those of the last sampling call, on the device;
+        `theta` (count, S, P) injects draws instead (test hook)."""
+        count = self.K - k0 if count is None else count
+        d = self.d
+        S = 0
+        if theta is not None:
+            theta = np.ascontiguousarray(theta, dtype=np.float64)
+            if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
+                raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
+            S = theta.shape[1]
+        if center is not None:
+            center = np.ascontiguousarray(center, dtype=np.float64)
+            if center.shape != (d,):
+                raise ValueError('center: ({},)'.format(d))
+        s = np.zeros(d)
+        sc = np.zeros((d, d), order='F') if want_scatter else None
+        n = ctypes.c_longlong()
+        check(self.lib.epx_pooled_moments(self.ctx, int(k0), int(count), dptr(center), dptr(theta), int(S),
+                                          1 if want_scatter else 0, dptr(s), dptr(sc), ctypes.byref(n)))
+        return n.value, s, sc
+
     def accept(self, df):
         check(self.lib.epx_accept(self.ctx, float(df)))
 

@@ -8,8 +8,11 @@ initial approximation prepended, and `kl_mvn` (plot_res.py:41-60) to score it.
 With `conf.mix` the final approximation is mixed from the last samples of all
 sites (`mix_phi`) and the group-level `alpha` / `beta` moments are stored as
 `m_<name>_ep` / `v_<name>_ep` (`mix_pred` with `_create_pmaps`, fit.py:408-421).
-The competing methods of fit.py (full model, consensus MC, target run) need
-Stan itself and are out of scope; asking for them raises NotImplementedError.
+`run_consensus` runs consensus Monte Carlo on the device (consensus.py, fit.py:537-675)
+and returns / saves `m_s_cons, S_s_cons, time_s_cons, mstepsize_s_cons, mrhat_s_cons`.
+The full-model and target runs of fit.py sample the JOINT model (P = 1122 coordinates
+at the default size), which no sampler layout here holds: `run_full`, `run_target`
+and `run_all`, which implies them, raise NotImplementedError.
 """
 
 import os
@@ -17,6 +20,7 @@ import os
 import numpy as np
 
 from . import models
+from .consensus import run_consensus
 from .method import Master
 from .util import invert_normal_params, distribute_groups
 
@@ -117,16 +121,20 @@ def _create_pmaps(phiers, J, K, Ns):
     return pmaps
 
 
-def main(model_name, conf, ret_master=False, verbose=True, _engine_factory=None, **master_kwargs):
-    """The `run_ep` branch of fit.py:210-459 for K == J.
+def main(model_name, conf, ret_master=False, verbose=True, _engine_factory=None, iters=None, **master_kwargs):
+    """The `run_ep` branch of fit.py:210-459 and the `run_consensus` branch of fit.py:537-675.
 
     Returns the dict that is saved to `res_d_<model>.npz` (or the Master when
-    `ret_master`)."""
+    `ret_master`).  With `conf.run_consensus` the consensus run follows (its iteration
+    counts: `iters`, default consensus.consensus_iters) and its keys are merged into the
+    returned dict; `run_consensus` without `run_ep` skips the EP run and returns the
+    consensus dict alone."""
     if not isinstance(conf, configurations):
         raise ValueError("Invalid arg. `conf`, use class fit.configurations")
-    if conf.run_full or conf.run_consensus or conf.run_target or conf.run_all:
-        raise NotImplementedError("only the distributed EP method (`run_ep`) is built; the full, "
-                                  "consensus and target runs need Stan itself")
+    if conf.run_full or conf.run_target or conf.run_all:
+        raise NotImplementedError("the full-model and target runs (`run_full`, `run_target`, and `run_all`, which "
+                                  "implies them) are not built: they sample the joint model, which no sampler "
+                                  "layout holds")
     J, D, K = conf.J, conf.D, conf.K
     if model_name not in models.MODELS:
         raise ValueError("unknown model {!r}; available: {}".format(model_name, sorted(models.MODELS)))
@@ -148,6 +156,8 @@ def main(model_name, conf, ret_master=False, verbose=True, _engine_factory=None,
         raise NotImplementedError("Splitting the groups not implemented.")               # fit.py:339-341
     if _engine_factory is not None:
         master_kwargs['_engine_factory'] = _engine_factory
+    if conf.run_consensus and not conf.run_ep and not ret_master:
+        return run_consensus(model_name, conf, model, data, iters=iters, verbose=verbose, **master_kwargs)
     if K < J:
         # several groups per site (fit.py:310-324): the multi-group program m*b.stan
         Nk, Nj_k, j_ind_k = distribute_groups(J, K, data.Nj)
@@ -189,5 +199,9 @@ def main(model_name, conf, ret_master=False, verbose=True, _engine_factory=None,
         np.savez(os.path.join(RES_PATH, fname), **res)
     if info:
         raise RuntimeError('epstan algorithm failed with error code: {}'.format(info))   # fit.py:405-408
+    if conf.run_consensus:
+        del epstan_master                   # (the consensus run builds its own sites: the prior to the power 1/K)
+        cons = run_consensus(model_name, conf, model, data, iters=iters, verbose=verbose, **master_kwargs)
+        res.update((k, v) for k, v in cons.items() if k != 'conf')
     res['phi_true'] = data.phi_true
     return res

@@ -276,6 +276,23 @@ int epx_named_len(epx_ctx *ctx, int k, int name, int *len);
 int epx_named_moments(epx_ctx *ctx, int k0, int count, const int32_t *names, int n_names,
                       const double *theta, int S, double *mean, double *m2, int *nsamp);
 
+/* Moments of the phi draws of the sites k0..k0+count POOLED: what the consensus run forms from the concatenated draws of
+ * all its sites (experiment/fit.py:639-646, `samp = np.concatenate(samples)`, and the `TODO make more efficient` there),
+ * taken from the draws where they lie in device memory.  Over all n = count * draws-per-site draws x:
+ *   sum[i] = sum (x_i - center_i),  scatter = sum (x - center)(x - center)' (d*d column-major, both triangles),
+ * d = dphi: only the first d coordinates of a draw record take part; the record stride is the context's P (in
+ * multi-group contexts the stride of the largest site; nothing behind a record's first d coordinates is read).
+ * center == NULL: 0.  want_scatter == 0: the sums alone, scatter may be NULL.  n out: the number of draws.
+ * theta == NULL: the draws of the last sampling call (error "no draws yet" before one, and an error when that call did
+ * not cover every site of the range), S is ignored; otherwise TEST HOOK: injected draws (count, S, P) row-major as
+ * epx_named_moments takes them.  No per-site factorisation and no S >= d requirement; the site arrays, the tilted
+ * moments and dQi / dri are neither read nor written.  Partial 16 x 16 tiles per slab of draws go to a workspace of the
+ * context and are added in a fixed order (no floating-point atomics): the same bits on every call.  Stream-ordered, one
+ * synchronisation. */
+int epx_pooled_moments(epx_ctx *ctx, int k0, int count, const double *center /* d, or NULL = 0 */,
+                       const double *theta, int S, int want_scatter,
+                       double *sum /* d */, double *scatter /* d*d column-major, may be NULL */, long long *n);
+
 /* ---------------------------------------------------------------------------------------------
  * Several GPUs: sites are sharded over the ranks (one context each); the only exchange of an EP
  * iteration is the reduction of method.py:1073-1074 (Q = sum_k Qi2 + Q0 over ALL sites) and the logical
