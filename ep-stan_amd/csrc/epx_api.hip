@@ -1231,6 +1231,96 @@ int epx_named_moments(epx_ctx *c, int k0, int count, const int32_t *names, int n
     return 0;
 }
 
+int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int32_t *row_group, const double *Xn,
+                const double *yn, const double *theta, int S, double *out, int *nsamp) {
+    CTX(c);
+    if (check_range(c, k0, count)) return -1;
+    if (!row_lim) return fail("epx_predict: row_lim is required");
+    if (c->D > EPX_PR_DMAX) return fail("epx_predict: D = %d columns, at most %d", c->D, (int)EPX_PR_DMAX);
+    if (row_lim[0] != 0) return fail("epx_predict: row_lim has to start at 0 (it starts at %lld)", (long long)row_lim[0]);
+    for (int j = 0; j < count; ++j)
+        if (row_lim[j + 1] < row_lim[j])
+            return fail("epx_predict: row_lim has to be non-decreasing (site %d: [%lld,%lld))", k0 + j,
+                        (long long)row_lim[j], (long long)row_lim[j + 1]);
+    const int64_t n = row_lim[count];
+    if (n > 0x7fffffff) return fail("epx_predict: %lld rows in one call, at most 2^31 - 1", (long long)n);
+    const size_t P = c->P, D = c->D;
+    PredictArgs a;
+    if (theta) {
+        if (S < 1) return fail("epx_predict: S = %d draws", S);
+    } else {
+        S = c->s_chains * c->s_nkeep;
+        if (!c->draws || S < 1 || c->drawn_count < 1) return fail("no draws yet");
+        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
+            return fail("epx_predict: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only",
+                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
+    }
+    if (nsamp) *nsamp = S;
+    if (n == 0) return 0;
+    if (!Xn || !out) return fail("epx_predict: Xn and out are required");
+    if (yn && !c->gauss)
+        for (int64_t i = 0; i < n; ++i)
+            if (yn[i] != 0.0 && yn[i] != 1.0)
+                return fail("epx_predict: row %lld: y = %g, the Bernoulli models take 0 or 1", (long long)i, yn[i]);
+    // rows sorted by (site, group), stable: perm[sorted position] = row; then workgroups of <= 64 rows of one (site, group)
+    std::vector<int> perm((size_t)n), at;
+    std::vector<PredictWg> wg;
+    for (int j = 0; j < count; ++j) {
+        const int ng = c->multi ? c->g_cnt[k0 + j] : 1;
+        const int64_t lo = row_lim[j], hi = row_lim[j + 1];
+        at.assign((size_t)ng + 1, 0);
+        for (int64_t i = lo; i < hi; ++i) {
+            const int g = row_group ? row_group[i] : 0;
+            if (g < 0 || g >= ng)
+                return fail("epx_predict: row %lld: group %d outside the %d group(s) of site %d", (long long)i, g, ng, k0 + j);
+            ++at[(size_t)g + 1];
+        }
+        for (int g = 0; g < ng; ++g) {
+            const int first = (int)lo + at[g], rows = at[g + 1];
+            for (int r = 0; r < rows; r += EPX_PR_WG_ROWS)
+                wg.push_back(PredictWg{j, g, first + r, rows - r < EPX_PR_WG_ROWS ? rows - r : (int)EPX_PR_WG_ROWS});
+            at[g + 1] += at[g];
+        }
+        for (int64_t i = lo; i < hi; ++i) perm[(size_t)lo + at[row_group ? row_group[i] : 0]++] = (int)i;
+    }
+    if (theta) {
+        const size_t need = (size_t)count * S * P;
+        HIPCHK(c->inj.grow(need));
+        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
+        a.draws = c->inj;
+    } else {
+        a.draws = c->draws + (size_t)k0 * S * P;
+    }
+    a.model = c->model; a.D = c->D; a.d = c->d; a.gauss = c->gauss; a.P = c->P; a.S = S;
+    a.KP = (1 + c->D + 3) / 4 * 4;
+    a.k0 = k0; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    const size_t nn = (size_t)n, nwg = wg.size();
+    HIPCHK(c->pred_ws.grow(nn * D + nn + nn * EPX_PR_COUNT));
+    HIPCHK(c->pred_iws.grow(4 * nwg + nn));
+    double *X_d = c->pred_ws, *y_d = X_d + nn * D, *out_d = y_d + nn;
+    int *wg_d = c->pred_iws, *perm_d = wg_d + 4 * nwg;
+    static_assert(sizeof(PredictWg) == 4 * sizeof(int), "PredictWg is four ints");
+    {
+        // `perm` and `wg` are this frame's: once their copies are queued nothing returns before the stream has been
+        // synchronised
+        hipError_t e = hipMemcpyAsync(X_d, Xn, nn * D * 8, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && yn) e = hipMemcpyAsync(y_d, yn, nn * 8, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(wg_d, wg.data(), nwg * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(perm_d, perm.data(), nn * sizeof(int), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) {
+            a.wg = reinterpret_cast<const PredictWg *>(wg_d); a.perm = perm_d;
+            a.X = X_d; a.y = yn ? y_d : nullptr; a.out = out_d;
+            hipLaunchKernelGGL(k_predict, dim3((unsigned)nwg), dim3(256), 0, c->stream, a);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(out, out_d, nn * EPX_PR_COUNT * 8, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream);
+        HIPCHK(e);
+        HIPCHK(es);
+    }
+    return 0;
+}
+
 int epx_pooled_moments(epx_ctx *c, int k0, int count, const double *center, const double *theta, int S, int want_scatter,
                        double *sum, double *scatter, long long *n) {
     CTX(c);

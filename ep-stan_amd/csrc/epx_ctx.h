@@ -104,6 +104,8 @@ struct epx_ctx {
     DevBuf<double> inj;             // injected samples (test hook)
     DevBuf<double> named_out;       // epx_named_moments: [mean | M2] records of the call
     DevBuf<double> pooled_ws;       // epx_pooled_moments: [partial tiles | partial sums | scatter | sum | centre]
+    DevBuf<double> pred_ws;         // epx_predict: [new rows (n x D) | responses (n) | results (n x EPX_PR_COUNT)]
+    DevBuf<int> pred_iws;           // ... [workgroup records (4 ints each) | sorted position -> row (n)]
     int has_last = 0;
     int nsamp = 0;                  // draws per site of the last tilted/moments call
     double last_df = 0.0;

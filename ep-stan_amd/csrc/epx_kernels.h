@@ -132,6 +132,24 @@ struct PooledArgs {
 __global__ void k_pooled_partial(PooledArgs a);
 __global__ void k_pooled_final(PooledArgs a);
 
+// Posterior predictive of new rows from the draws in device memory (predict.hip; include/epx.h: epx_predict).  The host
+// sorts the new rows by (site, group) and cuts them into workgroups of at most 64 rows of ONE (site, group).
+enum { EPX_PR_TILE = 16, EPX_PR_WG_ROWS = 64, EPX_PR_DMAX = 128 };
+struct PredictWg { int site, group, first, rows; };   // site of the call; first sorted row; rows <= EPX_PR_WG_ROWS
+struct PredictArgs {
+    int model, D, d, gauss, P, S;
+    int KP;                            // 1 + D (alpha's leading 1 and the D columns) rounded up to a multiple of 4
+    int k0;                            // first site (absolute: indexes site_g0)
+    const int *site_g0;                // prefix sums of the groups per site, or NULL: one group everywhere
+    const double *draws;               // site b of the call at draws + b * S * P: (S, P) row-major
+    const PredictWg *wg;               // one per workgroup
+    const int *perm;                   // sorted position -> row of the caller
+    const double *X;                   // n x D row-major, the caller's order
+    const double *y;                   // n, or NULL: no LPD
+    double *out;                       // n x EPX_PR_COUNT, the caller's order
+};
+__global__ void k_predict(PredictArgs a);
+
 __global__ void k_cavity(CavityArgs a);
 __global__ void k_moments(MomentArgs a);
 __global__ void k_site_sums_partial(SumArgs a);

@@ -8,60 +8,15 @@
 // them in NumPy).  Two passes -- mean first, then sum (x - mean)^2 -- never sum x^2 - n mean^2.
 #include "epx_device.h"
 #include "epx_kernels.h"
+#include "named_elem.h"
 
 namespace epx {
 
-// How one output element is formed from the coordinates of a draw.
-enum { NM_ZERO = 0, NM_ID, NM_EXP, NM_MUL, NM_MULADD };
-struct NamedElem {
-    int kind;       // ZERO: behind the site's own groups; ID: th[ia]; EXP: exp(th[ia]); MUL: th[ia] * exp(th[ib]);
-    int ia, ib, ic; // MULADD: th[ic] + th[ia] * exp(th[ib])
-};
-
+// output element e of a call's row: element r of its n-th requested name (named_elem.h)
 __device__ inline NamedElem named_elem(const NamedArgs &a, int e, int ng) {
     int n = 0;
     while (n + 1 < a.n_names && e >= a.off[n + 1]) ++n;
-    const int r = e - a.off[n];
-    const int model = a.model, D = a.D, d = a.d;
-    const int o = a.gauss ? 1 : 0;                       // the Gaussian family's log sigma sits in front of the b-model's phi
-    const bool hier = model >= EPX_M4B_SG;               // phi = [mu_a, log sigma_a, mu_b (D), log sigma_b (D)]
-    const int lsa = o + (hier ? 1 : 0);                  // log sigma_a
-    NamedElem el = {NM_ZERO, 0, 0, 0};
-    if (r >= named_len(a.name[n], model, D, d, a.gauss, ng)) return el;       // padding up to the largest site
-    switch (a.name[n]) {
-    case EPX_NM_PHI: el.kind = NM_ID; el.ia = r; break;
-    case EPX_NM_ETA: el.kind = NM_ID; el.ia = d + r; break;
-    case EPX_NM_ALPHA:
-        el.kind = hier ? NM_MULADD : NM_MUL; el.ia = d + r; el.ib = lsa; el.ic = o;
-        break;
-    case EPX_NM_BETA: {
-        const int j = r % D;
-        el.ia = d + ng + r;
-        if (model == EPX_M1B_SG) { el.kind = NM_ID; el.ia = o + 1 + r; }
-        else if (model == EPX_M2B_SG) { el.kind = NM_MUL; el.ib = o + 1; }
-        else if (model == EPX_M3B_SG) { el.kind = NM_MUL; el.ib = o + 1 + j; }
-        else { el.kind = NM_MULADD; el.ib = o + 2 + D + j; el.ic = o + 2 + j; }
-        break;
-    }
-    case EPX_NM_SIGMA_A: el.kind = NM_EXP; el.ia = lsa; break;
-    case EPX_NM_ETB: el.kind = NM_ID; el.ia = d + ng + r; break;
-    case EPX_NM_SIGMA_B: el.kind = NM_EXP; el.ia = hier ? o + 2 + D + r : o + 1 + r; break;
-    case EPX_NM_MU_A: el.kind = NM_ID; el.ia = o; break;
-    case EPX_NM_MU_B: el.kind = NM_ID; el.ia = o + 2 + r; break;
-    case EPX_NM_SIGMA: el.kind = NM_EXP; el.ia = 0; break;
-    default: break;
-    }
-    return el;
-}
-
-__device__ inline double named_value(const NamedElem &el, const double *th) {
-    switch (el.kind) {
-    case NM_ID: return th[el.ia];
-    case NM_EXP: return exp_d(th[el.ia]);
-    case NM_MUL: return th[el.ia] * exp_d(th[el.ib]);
-    case NM_MULADD: return th[el.ic] + th[el.ia] * exp_d(th[el.ib]);
-    default: return 0.0;
-    }
+    return named_elem_of(a.name[n], e - a.off[n], a.model, a.D, a.d, a.gauss, ng);
 }
 
 // Grid: one workgroup per site, 256 threads.  thread = (element, slice of the draws): consecutive lanes take consecutive

@@ -511,6 +511,39 @@ class HipEngine(object):
             m2s.append(dv)
         return n.value, means, m2s
 
+    def predict(self, Xn, row_lim, row_group=None, y=None, k0=0, count=None, theta=None):
+        """Posterior predictive of new rows (epx_predict, include/epx.h): (n, 4), columns site_params.PR_MEAN,
+        PR_F_MEAN, PR_F_M2, PR_LPD (NaN without y).  Xn (n, D); the rows of site k0 + j are
+        [row_lim[j], row_lim[j+1]); row_group (n): 0-based group within the row's site (None: 0).  The draws are those
+        of the last sampling call, on the device; `theta` (count, S, P) injects draws instead (test hook)."""
+        count = self.K - k0 if count is None else count
+        row_lim = np.ascontiguousarray(row_lim, dtype=np.int64)
+        if row_lim.shape != (count + 1,):
+            raise ValueError('row_lim: count + 1 = {} row limits'.format(count + 1))
+        n = int(row_lim[-1])
+        Xn = np.ascontiguousarray(Xn, dtype=np.float64)
+        if Xn.ndim != 2 or Xn.shape[1] != self.D or Xn.shape[0] != n:
+            raise ValueError('Xn: (n, D) = ({}, {})'.format(n, self.D))
+        if row_group is not None:
+            row_group = np.ascontiguousarray(row_group, dtype=np.int32)
+            if row_group.shape != (Xn.shape[0],):
+                raise ValueError('row_group: one group per new row')
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.float64)
+            if y.shape != (Xn.shape[0],):
+                raise ValueError('y: one response per new row')
+        S = 0
+        if theta is not None:
+            theta = np.ascontiguousarray(theta, dtype=np.float64)
+            if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
+                raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
+            S = theta.shape[1]
+        out = np.zeros((Xn.shape[0], _site_params.PR_COUNT))
+        check(self.lib.epx_predict(self.ctx, int(k0), int(count), row_lim.ctypes.data_as(_lib.c_int64_p),
+                                   row_group.ctypes.data_as(_lib.c_int32_p) if row_group is not None else None,
+                                   dptr(Xn), dptr(y), dptr(theta), int(S), dptr(out), None))
+        return out
+
     def pooled_moments(self, center=None, k0=0, count=None, theta=None, want_scatter=True):
         """Moments of the phi draws of the sites k0..k0+count pooled (epx_pooled_moments, include/epx.h): (n, sum, scatter)
         with n the number of draws, sum (d) = sum (x - center) and scatter (d, d) = sum (x - center)(x - center)', None

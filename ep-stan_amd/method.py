@@ -729,6 +729,109 @@ class Master(object):
             return mean[0], var[0]
         return mean, var
 
+    def _local_predict(self, Xn, row_lim, group, y):
+        """Prediction records (n_local, 4) of new rows of this rank's sites (see HipEngine.predict).  The device engine
+        computes them next to the draws; an engine without `predict` (the CPU oracle the tests inject) hands its draws
+        to site_params.predict_host."""
+        eng = self.engine
+        if hasattr(eng, 'predict'):
+            return eng.predict(Xn, row_lim, group, y)
+        mid, gauss, _ = self._site_spec()
+        out = np.zeros((Xn.shape[0], _site_params.PR_COUNT))
+        for j in range(self.K_local):
+            lo, hi = int(row_lim[j]), int(row_lim[j + 1])
+            if hi > lo:
+                out[lo:hi] = _site_params.predict_host(
+                    mid, self.D, int(self._site_ng[self.k_lo + j]), gauss, eng.get_draws(j, all_params=True), Xn[lo:hi],
+                    None if group is None else group[lo:hi], None if y is None else y[lo:hi])
+        return out
+
+    def predict(self, X_new, site_sizes=None, site_ind=None, j_ind=None, y_new=None):
+        """Posterior predictive of new rows from the tilted draws of the last iteration: what the fitted site models
+        predict for rows that were not part of the data (the reference has no counterpart: its user extracts every
+        draw and re-applies the models' `transformed parameters`).
+
+        X_new (n, D); the site of every row either as `site_sizes` (K counts, rows ordered by site; a site may have
+        none) or as `site_ind` (n site indices, any order) -- exactly one of the two, with the constructor's meaning;
+        j_ind: the 1-based group of every row within its site, as in `A_n['j_ind']` (needed by the multi-group models,
+        refused by the `_sg` ones); y_new: responses of the new rows, for the log predictive density.
+
+        Returns a dict: `mean` (n) the predictive mean of y (of sigmoid(f) for the Bernoulli-logit models, of f for the
+        Gaussian ones), `f_mean` and `f_var` (n) mean and variance over the draws of the linear predictor
+        f = alpha + x . beta, `lpd` (n) log mean_s p(y | draw s) or None without `y_new`, `n` the draws per site;
+        rows in the caller's order.  The draws stay in device memory, the kernel k_predict reduces them to four
+        numbers per row.  With several ranks every rank computes the rows of its own sites and one all-reduce makes
+        every rank return the same result."""
+        if self.iter == 0:
+            raise RuntimeError("Can not predict before at least one iteration has been done.")
+        if self._draws_injected:
+            raise RuntimeError("The draws of the last iteration were injected (`_sample_injector`): they hold phi "
+                               "only, nothing can be predicted from them.")
+        if (site_sizes is None) == (site_ind is None):
+            raise ValueError("Give exactly one of `site_sizes` and `site_ind`")
+        X_new = np.asarray(X_new, dtype=np.float64)
+        if X_new.ndim != 2 or X_new.shape[1] != self.D:
+            raise ValueError("Argument `X_new` should be two dimensional with {} columns".format(self.D))
+        n, K = X_new.shape[0], self.K
+        order = None
+        if site_sizes is not None:
+            cnt = np.asarray(site_sizes, dtype=np.int64)
+            if cnt.shape != (K,) or np.any(cnt < 0) or cnt.sum() != n:
+                raise ValueError("`site_sizes`: {} non-negative counts that add up to the rows of `X_new`".format(K))
+        else:
+            site_ind = np.asarray(site_ind)
+            if site_ind.shape != (n,) or not np.issubdtype(site_ind.dtype, np.integer) \
+                    or (n and (site_ind.min() < 0 or site_ind.max() >= K)):
+                raise ValueError("`site_ind`: one site index in [0, {}) per row of `X_new`".format(K))
+            order = np.argsort(site_ind, kind='mergesort')       # stable: rows keep their order inside a site
+            cnt = np.bincount(site_ind, minlength=K).astype(np.int64)
+        lim = np.concatenate(([0], np.cumsum(cnt)))
+        rows = np.arange(n) if order is None else order          # caller's row of every sorted row
+        mid, gauss, sg = self._site_spec()
+        group = None
+        if sg:
+            if j_ind is not None:
+                raise ValueError("site model {!r} holds one group per site: it takes no `j_ind`".format(self.model_name))
+        else:
+            if j_ind is None:
+                raise ValueError("site model {!r} holds several groups per site: give the 1-based group of every "
+                                 "new row within its site as `j_ind`".format(self.model_name))
+            j_ind = np.asarray(j_ind)
+            if j_ind.shape != (n,) or not np.issubdtype(j_ind.dtype, np.integer):
+                raise ValueError("`j_ind`: one integer per row of `X_new`")
+            group = (j_ind[rows] - 1).astype(np.int32)
+            bad = np.nonzero((group < 0) | (group >= np.repeat(self._site_ng, cnt)))[0]
+            if bad.size:
+                i = int(bad[0])
+                k = int(np.searchsorted(lim, i, side='right') - 1)
+                raise ValueError("`j_ind` of row {}: group {} outside 1..{} of site {}"
+                                 .format(int(rows[i]), int(group[i]) + 1, int(self._site_ng[k]), k))
+        ys = None
+        if y_new is not None:
+            y_new = np.asarray(y_new, dtype=np.float64)
+            if y_new.shape != (n,):
+                raise ValueError("The shapes of `y_new` and `X_new` does not match")
+            bad = np.nonzero((y_new != 0) & (y_new != 1))[0]
+            if not gauss and bad.size:
+                raise ValueError("`y_new` of row {}: {}; site model {!r} takes responses 0 or 1"
+                                 .format(int(bad[0]), y_new[bad[0]], self.model_name))
+            ys = np.ascontiguousarray(y_new[rows])
+        Xs = np.ascontiguousarray(X_new[rows])
+        lo, hi = int(lim[self.k_lo]), int(lim[self.k_hi])
+        rec = np.zeros((n, _site_params.PR_COUNT))
+        rec[lo:hi] = self._local_predict(Xs[lo:hi], lim[self.k_lo:self.k_hi + 1] - lo,
+                                         None if group is None else group[lo:hi], None if ys is None else ys[lo:hi])
+        if ys is None:
+            rec[:, _site_params.PR_LPD] = 0.0                    # (NaN without responses: nothing to add up)
+        if n:
+            rec = self.comm.allreduce_sum(rec)
+        out = np.empty_like(rec)
+        out[rows] = rec
+        S = self.engine.num_draws()
+        return dict(mean=out[:, _site_params.PR_MEAN].copy(), f_mean=out[:, _site_params.PR_F_MEAN].copy(),
+                    f_var=out[:, _site_params.PR_F_M2] / (S - 1),
+                    lpd=out[:, _site_params.PR_LPD].copy() if ys is not None else None, n=S)
+
     # a site whose slowest chain took more than this fraction of the iteration's slowest chain is
     # scheduled one workgroup per chain next time (measured leapfrog: 5.6 vs 10.3 us at D=32, n=500)
     LEAD_FRACTION = 0.4

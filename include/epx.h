@@ -293,6 +293,27 @@ int epx_pooled_moments(epx_ctx *ctx, int k0, int count, const double *center /* 
                        const double *theta, int S, int want_scatter,
                        double *sum /* d */, double *scatter /* d*d column-major, may be NULL */, long long *n);
 
+/* Posterior predictive of NEW rows from the draws of the sites k0..k0+count (no counterpart in the reference, whose user
+ * extracts every draw and re-applies the models' `transformed parameters` by hand).  For a new row x_i in group g of a
+ * site and every draw s of that site, f_si = alpha_g(s) + x_i . beta_g(s), with alpha and beta as EPX_NM_ALPHA /
+ * EPX_NM_BETA above form them.  Per row, over the site's S draws:
+ *   EPX_PR_MEAN    (1/S) sum_s sigmoid(f_si) for the Bernoulli-logit models, (1/S) sum_s f_si for the Gaussian ones;
+ *   EPX_PR_F_MEAN  (1/S) sum_s f_si;
+ *   EPX_PR_F_M2    sum_s (f_si - F_MEAN)^2, centred, in a second pass;
+ *   EPX_PR_LPD     log (1/S) sum_s exp(ll_si) with ll = y f - log(1 + e^f), or the logarithm of the normal density of y at
+ *                  mean f and scale exp(phi_s[0]); a log-mean-exp about the row's largest ll; NaN when yn == NULL.
+ * The rows are given by site: those of site k0 + j are [row_lim[j], row_lim[j+1]), row_lim[0] = 0, n = row_lim[count];
+ * a site or a group may have none, n == 0 returns without a launch.  row_group: 0-based group within the row's site, in
+ * any order (NULL: group 0 everywhere).  Xn (n x D row-major), yn (n; 0 or 1 for the Bernoulli models) and out
+ * (n x EPX_PR_COUNT row-major) are host arrays.  theta == NULL: the draws of the last sampling call (error "no draws
+ * yet" before one, and an error when that call did not cover every site of the range), S is ignored; otherwise TEST HOOK:
+ * injected draws (count, S, P) row-major as epx_named_moments takes them (a site reads its own coordinates of a record
+ * only).  nsamp out (may be NULL): draws per site.  At most D = 128 columns.  No floating-point atomics: the same bits
+ * on every call.  Stream-ordered, one launch, one synchronisation. */
+enum epx_pred { EPX_PR_MEAN = 0, EPX_PR_F_MEAN, EPX_PR_F_M2, EPX_PR_LPD, EPX_PR_COUNT };
+int epx_predict(epx_ctx *ctx, int k0, int count, const int64_t *row_lim, const int32_t *row_group, const double *Xn,
+                const double *yn, const double *theta, int S, double *out, int *nsamp);
+
 /* ---------------------------------------------------------------------------------------------
  * Several GPUs: sites are sharded over the ranks (one context each); the only exchange of an EP
  * iteration is the reduction of method.py:1073-1074 (Q = sum_k Qi2 + Q0 over ALL sites) and the logical
