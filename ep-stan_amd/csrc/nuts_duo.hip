@@ -397,7 +397,28 @@ __device__ __forceinline__ void duo_piece(DuoArgsK *kargs_p, int tid, bool queue
                 }
                 alpha_c = sl[JOB];
                 // ---- cavity term Omega V of the four chains
-                if (g_on) {
+                // (wave 3 with a whole group AND the rows beyond the groups: the tail's operands are requested with the
+                // group's and its products go between the group's as a third chain, instead of a chain of NJT dependent
+                // products behind a round trip of their own -- the team's barrier waits for this wave)
+                const bool t_in = NGF == 4 && t_on && g_on;
+                if (t_in) {
+                    double vt[NJT];
+#pragma unroll
+                    for (int J = 0; J < NJ; ++J) vb[J] = sl[VOFF + 4 * J + hi];
+#pragma unroll
+                    for (int tt = 0; tt < NJT; ++tt) vt[tt] = sl[VOFF + 4 * (4 * tt + bb) + hi];
+                    double acc = 0.0, acc1 = 0.0, acct = 0.0;
+#pragma unroll
+                    for (int J = 0; J < NJ; J += 2) {
+                        acc = mfma4(om[J], vb[J], acc);
+                        if (J + 1 < NJ) acc1 = mfma4(om[J + 1 < NJ ? J + 1 : J], vb[J + 1 < NJ ? J + 1 : J], acc1);
+                        if (J / 2 < NJT) acct = mfma4(omt[J / 2 < NJT ? J / 2 : 0], vt[J / 2 < NJT ? J / 2 : 0], acct);
+                    }
+                    static_assert(NGF != 4 || (NJ + 1) / 2 >= NJT, "the tail's products fit between the group's");
+                    sl[OVOFF + 16 * wr + rb] = acc + acc1;
+                    acct += dpp_d<0x124>(acct); acct += dpp_d<0x128>(acct);          // the four blocks' k-shares (row_ror 4, 8)
+                    if (bb == 0) sl[OVOFF + 16 * NGF + hi] = acct;
+                } else if (g_on) {
                     // (all B operands requested first: a product behind its own LDS round trip would pay the latency 17 times;
                     // k-steps beyond d meet zero A operands)
 #pragma unroll
@@ -410,7 +431,7 @@ __device__ __forceinline__ void duo_piece(DuoArgsK *kargs_p, int tid, bool queue
                     }
                     sl[OVOFF + 16 * wr + rb] = acc + acc1;
                 }
-                if (t_on) {
+                if (t_on && !t_in) {
                     double vt[NJT];
 #pragma unroll
                     for (int tt = 0; tt < NJT; ++tt) vt[tt] = sl[VOFF + 4 * (4 * tt + bb) + hi];
