@@ -49,7 +49,7 @@ namespace epx {
 // stores drained by every storing wave's vmcnt(0), a workgroup barrier, one lane's flag store; the consumer's acquire kept),
 // measured there on gfx950 / ROCm 7.2 and marked "not an architectural guarantee".  This is an argument from the ISA's behaviour, not from the language's memory model (for which a
 // relaxed store orders nothing): it is therefore (a) confined to this header, (b) switchable -- -DEPX_PIECE_FENCE puts the
-// release fence and a release store back, build.sh ships that build as variants/libepx_fence.so -- and (c) tested on the
+// release fence and a release store back, the Makefile ships that build as variants/libepx_fence.so -- and (c) tested on the
 // device by a litmus run (tests/test_gpu_round4.py::test_piece_handoff_litmus_*: hundreds of sites in pieces of ONE
 // transition, so that every site changes XCD dozens of times per launch, repeated, bit-equal to the uncut launch, under
 // both builds).  Every piece boundary has its own record (piece_record), so no address is ever written twice in a launch.

@@ -6,15 +6,6 @@
 #   EPX_LIB=$PWD/variants/libepx_sched_minreg.so python -m pytest tests -m gpu -q \
 #       --deselect tests/test_gpu_parity.py::test_native_library_is_loaded                          (on the box)
 # Results must not depend on the schedule: every draw-by-draw test passes under iterative-minreg and max-ilp.
-set -e
-cd "$(dirname "$0")/../ep-stan_amd/csrc"
 name=$1; shift
-mkdir -p build_var ../../variants
-objs=""
-for tu in dense nuts nuts_duo nuts_stream; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off "$@" -c $tu.hip -o build_var/${tu}_sched_$name.o &
-  objs="$objs build_var/${tu}_sched_$name.o"
-done
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../variants/libepx_sched_$name.so $objs build/epx_api.o build/epx_comm.o -ldl
-echo built variants/libepx_sched_$name.so
+# (TUS reaches make unexpanded: the Makefile's own list of the kernel translation units)
+exec "$(dirname "$0")/../ep-stan_amd/csrc/build.sh" variant NAME="sched_$name" 'TUS=$(KERNEL_TUS)' EXTRA="$*"
