@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/epx.h"
+#include "nuts_geometry.h"
 
 // error message kept per thread, returned by epx_last_error(); always returns -1
 int epx_fail(const char *fmt, ...);
@@ -64,7 +65,7 @@ struct DevBuf {
     }
 };
 
-static const size_t LDS_CAP = 160 * 1024;
+static const size_t LDS_CAP = epx::lds_capacity();
 
 struct epx_ctx {
     int device = 0, model = 0, K = 0, D = 0, d = 0, P = 0;

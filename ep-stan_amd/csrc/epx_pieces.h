@@ -210,4 +210,22 @@ __device__ __forceinline__ void piece_release(Args &a, unsigned char *smem) {
 #endif
 }
 
+// ------------------------------------------------------------------ host side
+// Workgroups of a launch with LOOPING workgroups (NutsArgs::persist): as many as the device holds of `kern` at a time, at
+// most 8 per CU (the host sized the workgroups' private memory for that many), never more than there are pieces.  The
+// kernel is allowed its `lds` bytes of dynamic LDS first: the occupancy is asked for that size.  Returns the hipError_t.
+template <class Kern>
+static int piece_looping_workgroups(Kern kern, int threads, size_t lds, int pieces, int *nwg) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    int per_cu = 0, dev = 0, ncu = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), threads, lds);
+    if (e != hipSuccess) return (int)e;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int hold = (per_cu > 0 ? (per_cu < 8 ? per_cu : 8) : 1) * (ncu > 0 ? ncu : 1);
+    *nwg = pieces < hold ? pieces : hold;
+    return (int)hipSuccess;
+}
+
 }  // namespace epx

@@ -35,7 +35,7 @@ k_nuts(NutsArgs a) {
     constexpr int LOG = Log2<DP>::v;
     constexpr int SPR = DP / 2;                       // 16-B slots per row
     constexpr int RPL = DP >= 32 ? 1 : 32 / DP;       // rows per 256-B bank line
-    constexpr int XREC = 64 * (1 + NV) + 2;           // per-wave exchange record (doubles)
+    constexpr int XREC = nuts_exchange_record(NV);    // per-wave exchange record (doubles)
     constexpr int SREC = nuts_stack_record(NV);       // per-level stack record (doubles)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -173,7 +173,7 @@ k_nuts(NutsArgs a) {
 enum { SPEC_NONE = 0, SPEC_RESTART = 1, SPEC_EXIT = 2 };
 
 template <int NV, int DP, bool RES, bool GAUSS, bool GRP>
-__global__ void __launch_bounds__(320)
+__global__ void __launch_bounds__(nuts_spec_threads())
 k_nuts_spec(NutsArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     using V = Vec<NV>;
@@ -182,10 +182,10 @@ k_nuts_spec(NutsArgs a) {
     constexpr int LOG = Log2<DP>::v;
     constexpr int SPR = DP / 2;
     constexpr int RPL = DP >= 32 ? 1 : 32 / DP;
-    constexpr int XREC = 64 * (1 + NV) + 2;
+    constexpr int XREC = nuts_exchange_record(NV);
     constexpr int SREC = nuts_stack_record(NV);
-    constexpr int MREC = 3 * NV * 64 + 4 + 64;        // mailbox: q, p, grad, ll, -, generation, -, per-lane lp terms
-    constexpr int CREC = 4 * NV * 64 + 4;             // control: q, p, grad, metric, eps_l, command, stamp
+    constexpr int MREC = nuts_spec_mail_record(NV);       // mailbox
+    constexpr int CREC = nuts_spec_control_record(NV);    // control
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool is_bk = wave == WPC;
@@ -198,10 +198,10 @@ k_nuts_spec(NutsArgs a) {
     const int64_t row0 = a.k_lim[k];
     const int n = (int)(a.k_lim[k + 1] - row0);
     // several groups per site (GRP): theta = [phi | eta (ng) | etb (ng x D)]; records stay a.P wide
-    constexpr int GREC = 66, WREC = 64 * NV + 2;        // per-group / per-wave exchange records (nuts_gradient_groups.inc)
+    constexpr int GREC = nuts_group_record(), WREC = nuts_wave_record(NV);        // per-group / per-wave exchange records (nuts_gradient_groups.inc)
     int ng = 1;
     int *gl_s = reinterpret_cast<int *>(smem + a.off_gl);
-    double *qcopy = reinterpret_cast<double *>(smem + a.off_gl) + ((a.ngmax + 1 + 3) / 4) * 2;     // behind the row limits, 16-B aligned
+    double *qcopy = reinterpret_cast<double *>(smem + a.off_gl) + nuts_group_limit_doubles(a.ngmax);     // behind the row limits, 16-B aligned
     (void)qcopy;
     if constexpr (GRP) {
         const int g0 = a.site_g0[k];
@@ -422,13 +422,13 @@ size_t nuts_lds_layout(NutsArgs &a, int wpc, int dp, int n_max) {
     if (a.grp) {
         // several groups per site: per-wave (Omega partials, ll) and per-group (dbeta, dalpha) records, both parities,
         // then the group row limits
-        off += (size_t)2 * (wpc * (64 * nv + 2) + (size_t)a.ngmax * 66) * 8;
+        off += (size_t)2 * nuts_group_exchange(nv, wpc, a.ngmax) * 8;
         a.off_gl = (int)off;
-        off += ((size_t)(a.ngmax + 1) * 4 + 15) & ~(size_t)15;
+        off += (size_t)nuts_group_limit_doubles(a.ngmax) * 8;
         off += (size_t)wpc * 2 * 64 * nv * 8;              // per-wave copies of q and exp(q)
-    } else if (wpc > 1) off += (size_t)2 * wpc * (64 * (1 + nv) + 2) * 8;
+    } else if (wpc > 1) off += (size_t)2 * wpc * nuts_exchange_record(nv) * 8;
     off = (off + 15) & ~(size_t)15;
-    const size_t cap = 160 * 1024;
+    const size_t cap = lds_capacity();
     const size_t om = (size_t)a.d * a.d * 8;
     a.om_in_lds = 0; a.off_Om = (int)off;
     if (off + om <= cap) { a.om_in_lds = 1; off += om; off = (off + 15) & ~(size_t)15; }
@@ -442,7 +442,7 @@ size_t nuts_lds_layout(NutsArgs &a, int wpc, int dp, int n_max) {
     // layout 2: room for the speculative kernel's mailbox / control records?
     a.off_spec = 0;
     if (wpc == 4 && a.cpb == 1 && a.om_in_lds == a.stack_in_lds) {
-        const size_t rec = (size_t)2 * ((3 * nv * 64 + 4 + 64) + (4 * nv * 64 + 4)) * 8;
+        const size_t rec = (size_t)2 * (nuts_spec_mail_record(nv) + nuts_spec_control_record(nv)) * 8;
         off = (off + 15) & ~(size_t)15;
         if (off + rec <= cap) { a.off_spec = (int)off; off += rec; }
     }
@@ -452,23 +452,12 @@ size_t nuts_lds_layout(NutsArgs &a, int wpc, int dp, int n_max) {
 
 template <int NV, int DP, bool RES, bool GAUSS = false, bool GRP = false>
 static int launch_spec(const NutsArgs &a, int nblocks, hipStream_t stream) {
-    auto kern = k_nuts_spec<NV, DP, RES, GAUSS, GRP>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(320), a.lds_bytes, stream, a);
-    return (int)hipGetLastError();
+    return launch_with_lds(k_nuts_spec<NV, DP, RES, GAUSS, GRP>, nblocks, nuts_spec_threads(), a.lds_bytes, stream, a);
 }
 
 template <int NV, int DP, int WPC, bool OML, bool STL, bool GAUSS = false>
 static int launch_one(const NutsArgs &a, int nblocks, hipStream_t stream) {
-    auto kern = k_nuts<NV, DP, WPC, OML, STL, GAUSS>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
-    if (e != hipSuccess) return (int)e;
-    const int threads = 64 * WPC * a.cpb;
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(threads), a.lds_bytes, stream, a);
-    return (int)hipGetLastError();
+    return launch_with_lds(k_nuts<NV, DP, WPC, OML, STL, GAUSS>, nblocks, 64 * WPC * a.cpb, a.lds_bytes, stream, a);
 }
 
 template <int NV, int DP>

@@ -287,4 +287,14 @@ __device__ __forceinline__ void flush_leaf_dh(int lane, int cnt, double dhb, dou
         }                                                                                                               \
     }
 
+// host side: how every sampler kernel is started -- the kernel is allowed `lds` bytes of dynamic LDS (beyond the 64 KB a
+// kernel may have unasked), launched, and the launch's error returned (hipError_t as int)
+template <class Kern>
+static int launch_with_lds(Kern kern, int nblocks, int threads, size_t lds, hipStream_t stream, const NutsArgs &a) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(threads), lds, stream, a);
+    return (int)hipGetLastError();
+}
+
 }  // namespace epx

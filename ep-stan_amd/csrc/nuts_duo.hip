@@ -143,20 +143,19 @@ __device__ __forceinline__ void duo_piece(DuoArgsK *kargs_p, int tid, bool queue
     constexpr int SPR = DP / 2;                       // 16-B slots per row
     constexpr int RPL = DP >= 32 ? 1 : 32 / DP;       // rows per 256-B bank line
     constexpr int SREC = nuts_stack_record(NV);       // per-level stack record (doubles)
-    constexpr int RES = DP + 2;                       // result of a row wave: X'g (DP), sum g, log-lik
+    constexpr int RES = duo_res(DP);                  // result of a row wave
     constexpr int JOB = 0;                            // job (alpha, beta): the head of the chain's slot ...
     // One chain per workgroup (RW > 1): [job RES | v = phi - mu (NV x 64) | per row wave: X'g, sum g, log-lik (RES) |
     // Omega v (NV x 64)] -- the cavity term is taken off the state wave, the longest role of this form, by a wave of
     // its own (O) that works beside the row waves
-    // (VN: doubles of the v and Omega v lines -- the TEAM form keeps only the d <= 2 DP + 2 live ones, in whole 16-byte
-    // pairs, and gives the LDS it saves to one more level of the tree stack)
-    constexpr int VN = (CPB == 4 && RW == 4 && 2 * DP + 8 < NV * 64) ? 2 * DP + 8 : NV * 64;
-    constexpr int VOFF = RES, RREC = RES, RESO = RES + VN, OVOFF = RESO + RW * RREC;
+    // (VN: doubles of the v and Omega v lines -- the TEAM form gives the LDS it saves on them to one more level of the tree stack)
+    constexpr int VN = duo_vn(NV, DP, CPB, RW);
+    constexpr int VOFF = duo_voff(DP), RREC = RES, RESO = duo_reso(NV, DP, CPB, RW), OVOFF = duo_ovoff(NV, DP, CPB, RW);
     // One chain per workgroup (CPB == 1): the tree bookkeeping gets a wave of its own (BK), as in k_nuts_spec --
     // the state wave integrates on speculatively and hands every finished state over through a two-entry mailbox;
     // BK answers with a control record only when the trajectory continues elsewhere (other tree end, new
     // transition, step-size trial): generation-numbered, states of an old generation are dropped.
-    constexpr bool BKW = CPB == 1;
+    constexpr bool BKW = duo_bkw(CPB);
     // Row TEAM (CPB == 4, RW == 4; layout 7): the four row waves are not a chain's own -- they serve the four chains of
     // the site together, in lock step, on the matrix pipe.  Pass p: every chain has posted job p; wave w takes a quarter
     // of the site's 16-row tiles through  F = alpha + X B  (v_mfma_f64_4x4x4: 16 rows x 4 chains per instruction), the
@@ -166,12 +165,12 @@ __device__ __forceinline__ void duo_piece(DuoArgsK *kargs_p, int tid, bool queue
     // jobs).  The rows are read from LDS twice per pass for FOUR gradients (eight times in the one-wave-per-chain form),
     // by instructions that cost one issue slot per 16 x 4 x 4 multiply-adds.  The state waves are the ones of the
     // RW > 1 form: they sum the four waves' partial results in wave order.
-    constexpr bool TEAM = CPB == 4 && RW == 4;
+    constexpr bool TEAM = duo_team(CPB, RW);
     constexpr int BOFF = TEAM ? 2 : 1;                // beta behind alpha in the job (TEAM: 16-byte aligned pairs)
     constexpr bool TBAR = TEAM;                       // the TEAM form's hand-offs are workgroup barriers (see team_barrier)
-    constexpr int MREC = 4 * NV * 64 + 4;             // mailbox entry: q, p, grad, per-element log-density terms; ll, -, generation, -
-    constexpr int CREC = 4 * NV * 64 + 4;             // control record: q, p, grad, metric, eps_l, command
-    constexpr int NFLAG = TEAM ? 1 : 1 + RW + (BKW ? 4 : 0);     // per chain: job, results, (mail, acknowledged, control generation, cavity term); TEAM: the job word, the team's four words behind the chains'
+    constexpr int MREC = duo_mail_record(NV);         // mailbox entry
+    constexpr int CREC = duo_control_record(NV);      // control record
+    constexpr int NFLAG = duo_nflag(CPB, RW);         // hand-off words per chain; TEAM: the job word, the team's words behind the chains'
 
 
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -202,7 +201,7 @@ __device__ __forceinline__ void duo_piece(DuoArgsK *kargs_p, int tid, bool queue
     const int D = a.D, d = a.d, P = a.P, model = a.model;
     const int64_t row0 = a.k_lim[k];
     const int n = (int)(a.k_lim[k + 1] - row0);
-    constexpr int OUP = NV > 1 ? 4 : 8;               // the cavity precision is zero padded to whole groups of OUP column pairs
+    constexpr int OUP = duo_ou(NV);                   // the cavity precision is zero padded to whole groups of OUP column pairs
     constexpr int OU = OUP;                           // column pairs per round of the mat-vec
     const int dm = d < 64 ? d : 64;                   // cavity precision: rows / columns held pair-interleaved
     const int tr = d - dm;                            // ... and the rows beyond (0..2 for D <= 32)
@@ -1498,7 +1497,7 @@ __device__ __forceinline__ void duo_piece(DuoArgsK *kargs_p, int tid, bool queue
 #undef a
 
 template <int NV, int DP, int CPB, int RW, bool STL, bool COLD, bool PIECED>
-__global__ void __launch_bounds__(64 * (CPB == 4 && RW == 4 ? 8 : CPB * (1 + RW) + (CPB == 1 ? 2 : 0)))
+__global__ void __launch_bounds__(duo_threads(CPB, RW))
 k_nuts_duo(NutsArgs a_by_value) {
     extern __shared__ __align__(16) unsigned char smem[];
     (void)a_by_value;
@@ -1549,7 +1548,7 @@ __device__ __attribute__((noinline)) void duo_piece_call(unsigned long long karg
 }
 
 template <int NV, int DP, int CPB, int RW, bool STL, bool COLD>
-__global__ void __launch_bounds__(64 * (CPB == 4 && RW == 4 ? 8 : CPB * (1 + RW) + (CPB == 1 ? 2 : 0)))
+__global__ void __launch_bounds__(duo_threads(CPB, RW))
 k_nuts_duo_loop(NutsArgs a_by_value) {
     extern __shared__ __align__(16) unsigned char smem[];
     (void)a_by_value;
@@ -1572,24 +1571,22 @@ k_nuts_duo_loop(NutsArgs a_by_value) {
 // host side: LDS layout + dispatch over the instantiated shapes
 size_t nuts_duo_lds_layout(NutsArgs &a, int cpb, int rw, int dp, int n_max) {
     const int nv = (a.P + 63) / 64;
-    const int ou = nv > 1 ? 4 : 8;                                                     // as the kernel (OU)
+    const int ou = duo_ou(nv);
     const int d = a.d, dm = d < 64 ? d : 64, npad = ((dm + 1) / 2 + ou - 1) / ou * ou;
-    const bool teamm = cpb == 4 && rw == 4;                                            // as the kernel (TEAM): whole 16-row tiles, no cavity precision in LDS
+    const bool teamm = duo_team(cpb, rw);                                              // whole 16-row tiles, no cavity precision in LDS
     size_t off = (size_t)(teamm ? team_rows(n_max) : n_max) * dp * 8;
     a.n_max = n_max; a.duo_rw = rw; a.cpb = cpb;
     a.off_Om = (int)off; off += teamm ? 0 : (size_t)npad * dm * 16;
     a.off_tail = (int)off; off += nv > 1 && !teamm ? (size_t)2 * (2 * npad + 2) * 8 : 0;
     off = (off + 15) & ~(size_t)15;
-    const int vn = (teamm && 2 * dp + 8 < nv * 64) ? 2 * dp + 8 : nv * 64;                           // as the kernel (VN)
-    a.slot_doubles = rw == 1 ? dp + 2 : (dp + 2) + vn + rw * (dp + 2) + vn;                         // as the kernel (VOFF, RESO, OVOFF)
+    a.slot_doubles = duo_slot_doubles(nv, dp, cpb, rw);
     a.off_slot = (int)off; off += (size_t)cpb * a.slot_doubles * 8;
-    const bool bkw = cpb == 1;                                                        // as the kernel (BKW)
-    a.off_flag = (int)off; off += teamm ? 48 : (size_t)cpb * (1 + rw + (bkw ? 4 : 0)) * 4;
+    a.off_flag = (int)off; off += (size_t)duo_flag_bytes(cpb, rw);
     off = (off + 15) & ~(size_t)15;
     a.off_spec = 0;
-    if (bkw) { a.off_spec = (int)off; off += (size_t)2 * ((4 * nv * 64 + 4) + (4 * nv * 64 + 4)) * 8; }
+    if (duo_bkw(cpb)) { a.off_spec = (int)off; off += (size_t)2 * (duo_mail_record(nv) + duo_control_record(nv)) * 8; }
     a.om_in_lds = 1;
-    const size_t cap = 160 * 1024;
+    const size_t cap = lds_capacity();
     const size_t stack = (size_t)cpb * a.max_depth * nuts_stack_record(nv) * 8;
     a.off_scr = 0;
     a.scr_doubles = (a.P + 7) & ~7;
@@ -1617,31 +1614,17 @@ size_t nuts_resident_chain_doubles(int nv, int max_depth) {
 
 template <int NV, int DP, int CPB, int RW>
 static int launch_duo_one(const NutsArgs &a, int nblocks, hipStream_t stream) {
-    auto go = [&](auto kern) -> int {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
-        if (e != hipSuccess) return (int)e;
-        constexpr int NT = 64 * (CPB == 4 && RW == 4 ? 8 : CPB * (1 + RW) + (CPB == 1 ? 2 : 0));
-        const int nb = nblocks;
-        (void)NT;
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(NT), a.lds_bytes, stream, a);
-        return (int)hipGetLastError();
-    };
+    constexpr int NT = duo_threads(CPB, RW);
+    auto go = [&](auto kern) -> int { return launch_with_lds(kern, nblocks, NT, a.lds_bytes, stream, a); };
     constexpr bool COLD = NV >= 2 || CPB > 1;
     if constexpr (COLD && CPB > 1) {
         if (a.dyn_prog && a.persist) {
-            // looping workgroups: as many as the device holds at a time (never more than there are pieces)
+            // looping workgroups (piece_looping_workgroups has set the kernel's LDS attribute: launched as it is)
             auto loop = [&](auto kern) -> int {
-                constexpr int NT = 64 * (CPB == 4 && RW == 4 ? 8 : CPB * (1 + RW));
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
-                if (e != hipSuccess) return (int)e;
-                int per_cu = 0, dev = 0, ncu = 0;
-                e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), NT, (size_t)a.lds_bytes);
-                if (e != hipSuccess) return (int)e;
-                (void)hipGetDevice(&dev);
-                (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-                const int hold = (per_cu > 0 ? (per_cu < 8 ? per_cu : 8) : 1) * (ncu > 0 ? ncu : 1);      // (the host sized the workgroups' private memory for at most 8 per CU)
-                hipLaunchKernelGGL(kern, dim3(nblocks < hold ? nblocks : hold), dim3(NT), a.lds_bytes, stream, a);
+                int nwg = 0;
+                const int e = piece_looping_workgroups(kern, NT, (size_t)a.lds_bytes, nblocks, &nwg);
+                if (e != (int)hipSuccess) return e;
+                hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), a.lds_bytes, stream, a);
                 return (int)hipGetLastError();
             };
             return a.stack_in_lds ? loop(k_nuts_duo_loop<NV, DP, CPB, RW, true, COLD>) : loop(k_nuts_duo_loop<NV, DP, CPB, RW, false, COLD>);

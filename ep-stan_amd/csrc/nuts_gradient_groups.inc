@@ -25,7 +25,7 @@
             const double a0 = model >= 3 ? elemU(zq, O) : 0.0;
             const double inv_s2 = GAUSS ? exp_d(-2.0 * elemU(zq, 0)) : 0.0;
             (void)inv_s2;
-            double *wrec = xch + (size_t)parity * (WPC * WREC + a.ngmax * GREC);       // per-wave records
+            double *wrec = xch + (size_t)parity * nuts_group_exchange(NV, WPC, a.ngmax);       // per-wave records
             double *grec = wrec + WPC * WREC;                                          // per-group records
             STAMP(0);
             // ---- likelihood, group by group: f = alpha_g + x.beta_g, res = y - sigmoid(f), acc += res x

@@ -43,6 +43,27 @@ static_assert(OM_UNROLL <= EPX_OM_PAD_COLS, "the cavity-column ring reads OM_UNR
 
 typedef const __attribute__((address_space(4))) NutsArgs StreamArgsK;    // the kernel arguments where they are: kernarg segment
 
+// LDS bytes of the streaming kernel: the engine's map, then the tail that stream_piece carves up behind it, just below
+// ("---- LDS carve-up") -- term by term in that order, under the kernel's names.  The two texts are kept in step by hand:
+// the kernel's carve-up is run-time code, which does not keep its machine code when it moves into a shared function
+// (DESIGN.md section 3.1).  nmax_res > 0: the resident variant (RES), dpb in {16, 32}.
+size_t nuts_stream_lds_bytes(int nv, int dpb, int d, int ngmax, int ntmax, int nmax_res, int gauss) {
+    const bool res = nmax_res > 0;
+    const size_t pmax = 64 * (size_t)nv;                           // PMAX
+    const size_t eng = res ? (dpb == 16 ? res_map<16>(nmax_res, ngmax, ntmax).end : res_map<32>(nmax_res, ngmax, ntmax).end)
+                           : (dpb == 64 ? stream_map<64>(ngmax, ntmax, gauss).end : stream_map<128>(ngmax, ntmax, gauss).end);    // eng_end
+    size_t dbl = 0;
+    dbl += (size_t)((d + 1) & ~1);                                 // mu_s
+    dbl += (size_t)d * NCH;                                        // vs4
+    dbl += res ? 0 : (size_t)d * NCH;                              // Ovs
+    dbl += NCH * pmax;                                             // q_s
+    dbl += NCH * pmax;                                             // eq_s
+    dbl += res ? (size_t)NCH * d * NCH : 0;                        // opart
+                                                                   // Om_s: d x d more when it fits (the caller adds them: a.om_in_lds)
+    dbl += 2;                                                      // sh_done and the tile count behind it (two ints, a 16-byte line)
+    return eng + dbl * 8;
+}
+
 // One piece of a site's run on the streaming layout: transitions [q_t0, q_t0 + piece length) of site q_site by the waves of
 // one workgroup (PIECED), or the whole run of the site blockIdx.x names.
 // RES: the resident variant (rows in LDS for the whole site update, 4 chain waves only, D <= 32)
@@ -557,18 +578,6 @@ k_nuts_stream_loop(NutsArgs a_by_value) {
     }
 }
 
-// LDS bytes of the streaming kernel
-size_t nuts_stream_lds_bytes(int nv, int dpb, int d, int ngmax, int ntmax, int nmax_res, int gauss) {
-    const size_t pmax = 64 * (size_t)nv;
-    size_t eng;
-    size_t dbl = (size_t)((d + 1) & ~1) + 2 * (size_t)d * NCH + 2 * NCH * pmax + 2;
-    if (nmax_res > 0) {             // resident variant: dpb in {16, 32}; per-wave Omega partials instead of Ovs
-        eng = dpb == 16 ? res_map<16>(nmax_res, ngmax, ntmax).end : res_map<32>(nmax_res, ngmax, ntmax).end;
-        dbl += (size_t)NCH * d * NCH - (size_t)d * NCH;
-    } else
-        eng = dpb == 64 ? stream_map<64>(ngmax, ntmax, gauss).end : stream_map<128>(ngmax, ntmax, gauss).end;
-    return eng + dbl * 8;
-}
 // doubles of global memory per chain: tree stack + cold store
 size_t nuts_stream_chain_doubles(int nv, int max_depth) {
     return (size_t)max_depth * nuts_stack_record(nv) + (size_t)COLD_VECS * 64 * nv;
@@ -581,25 +590,13 @@ static int launch_stream_one(const NutsArgs &a, int nblocks, size_t lds, hipStre
         if (a.dyn_prog) {
             kern = k_nuts_stream<NV, DPB, RES, true>; nblocks = a.seg_nwg;
             if (a.persist) {
-                // looping workgroups: as many as the device holds at a time (never more than there are pieces)
-                kern = k_nuts_stream_loop<NV, DPB>;
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return (int)e;
-                int per_cu = 0, dev = 0, ncu = 0;
-                e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), STREAM_THREADS, lds);
-                if (e != hipSuccess) return (int)e;
-                (void)hipGetDevice(&dev);
-                (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-                const int hold = (per_cu > 0 ? (per_cu < 8 ? per_cu : 8) : 1) * (ncu > 0 ? ncu : 1);      // (the host sized the workgroups' private memory for at most 8 per CU)
-                if (nblocks > hold) nblocks = hold;
+                kern = k_nuts_stream_loop<NV, DPB>;       // looping workgroups: as many as the device holds at a time
+                const int e = piece_looping_workgroups(kern, STREAM_THREADS, lds, nblocks, &nblocks);
+                if (e != (int)hipSuccess) return e;
             }
         }
     }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(RES ? 256 : STREAM_THREADS), lds, stream, a);
-    return (int)hipGetLastError();
+    return launch_with_lds(kern, nblocks, RES ? 256 : STREAM_THREADS, lds, stream, a);
 }
 
 template <int DPB, bool RES>

@@ -22,6 +22,7 @@ import tree_ending_cases as tc
 from oracle import nuts_oracle as no
 
 CASES = tc.cases()
+HERE = os.path.dirname(os.path.abspath(__file__))
 _runs = {}
 
 
@@ -34,18 +35,23 @@ def _oracle(case, fast=False):
     return _runs[key]
 
 
+def _build_probe(tmp_path, name):
+    """tests/<name>.hip compiled and linked with the tree's libepx.so; returns the program's path."""
+    from epstan_amd import _lib
+    hipcc = os.environ.get('HIPCC') or shutil.which('hipcc') or '/opt/rocm/bin/hipcc'      # (the compiler that built the library)
+    assert os.path.exists(_lib.LIB_PATH), 'libepx.so is not built'
+    exe = str(tmp_path / name)
+    libdir = os.path.dirname(os.path.abspath(_lib.LIB_PATH))
+    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O1', '-std=c++17', os.path.join(HERE, name + '.hip'), '-o', exe,
+                           '-L' + libdir, '-l:' + os.path.basename(_lib.LIB_PATH), '-Wl,-rpath,' + libdir])
+    return exe
+
+
 def test_stack_plan_is_the_librarys(tmp_path):
     """tree_ending_cases.STACK_PLAN against the library's own LDS planning functions, called by a small program linked
     with libepx.so (tests/stack_plan_probe.hip): at (16, 48) the whole tree stack is in LDS, at (32, 500) it spills --
     layouts 1 and 5 keep all of it in global memory, layout 7 its levels 3 and up, from max_depth 3 on."""
-    from epstan_amd import _lib
-    hipcc = os.environ.get('HIPCC') or shutil.which('hipcc') or '/opt/rocm/bin/hipcc'      # (the compiler that built the library)
-    assert os.path.exists(_lib.LIB_PATH), 'libepx.so is not built'
-    here = os.path.dirname(os.path.abspath(__file__))
-    exe = str(tmp_path / 'stack_plan_probe')
-    libdir = os.path.dirname(os.path.abspath(_lib.LIB_PATH))
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O1', '-std=c++17', os.path.join(here, 'stack_plan_probe.hip'), '-o', exe,
-                           '-L' + libdir, '-l:' + os.path.basename(_lib.LIB_PATH), '-Wl,-rpath,' + libdir])
+    exe = _build_probe(tmp_path, 'stack_plan_probe')
     for (D, n), by_depth in tc.STACK_PLAN.items():
         d, P = no.dims('m4b_sg', D)
         for md, want in by_depth.items():
@@ -59,6 +65,21 @@ def test_stack_plan_is_the_librarys(tmp_path):
             assert set(depths) | {10} <= set(tc.STACK_PLAN[(D, n)])
     spill = tc.STACK_PLAN[(32, 500)]
     assert spill[2][7] == (1, 0) and spill[3][7] == (0, 3) and spill[4][7] == (0, 3)      # the depths 2 | 3 | 4 straddle both boundaries
+
+
+def test_lds_plan_is_unchanged(tmp_path):
+    """Every field the LDS planning functions write (nuts_lds_layout, nuts_duo_lds_layout) and nuts_stream_lds_bytes, over
+    the sweep of tests/lds_plan_probe.hip, against tests/golden/lds_plan.txt -- the same program's output from the library
+    as it was when the host wrote the kernels' record sizes out a second time (before csrc/nuts_geometry.h).  Line for
+    line; the ALL line stands for the 15 120 plans of the whole cross product."""
+    exe = _build_probe(tmp_path, 'lds_plan_probe')
+    got = subprocess.check_output([exe]).decode().splitlines()
+    with open(os.path.join(HERE, 'golden', 'lds_plan.txt')) as f:
+        want = f.read().splitlines()
+    assert len(want) == 1717 and sum(line.startswith('ALL 15120 ') for line in want) == 1
+    assert len(got) == len(want)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, (i + 1, g, w)
 
 
 @pytest.mark.parametrize('case', CASES, ids=repr)
