@@ -92,6 +92,8 @@ SIGNATURES = {
                                           ctypes.c_int, c_double_p, c_double_p, ctypes.POINTER(ctypes.c_longlong)]),
     'epx_predict': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int64_p, c_int32_p, c_double_p, c_double_p,
                                    c_double_p, ctypes.c_int, c_double_p, c_int_p]),
+    'epx_draw_diagnostics': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int,
+                                            ctypes.c_int, c_double_p, c_int_p]),
     'epx_damp_sweep': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, ctypes.c_void_p,
                                       c_double_p, c_double_p, ctypes.c_double, c_double_p, c_double_p, ctypes.c_int,
                                       c_double_p]),

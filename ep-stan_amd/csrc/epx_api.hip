@@ -1321,6 +1321,49 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
     return 0;
 }
 
+int epx_draw_diagnostics(epx_ctx *c, int k0, int count, const double *theta, int S, int chains, double *out, int *nsamp) {
+    CTX(c);
+    if (check_range(c, k0, count)) return -1;
+    if (!out) return fail("epx_draw_diagnostics: out is required");
+    const size_t P = c->P;
+    DiagArgs a;
+    if (theta) {
+        if (S < 1) return fail("epx_draw_diagnostics: S = %d draws", S);
+        if (chains < 1 || chains > EPX_DG_MAX_CHAINS)
+            return fail("epx_draw_diagnostics: chains must be in 1..%d (got %d)", (int)EPX_DG_MAX_CHAINS, chains);
+        if (S % chains != 0) return fail("epx_draw_diagnostics: S = %d draws are no multiple of chains = %d", S, chains);
+        const size_t need = (size_t)count * S * P;
+        HIPCHK(c->inj.grow(need));
+        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
+        a.draws = c->inj;
+    } else {
+        chains = c->s_chains;
+        S = c->s_chains * c->s_nkeep;
+        if (!c->draws || S < 1 || c->drawn_count < 1) return fail("no draws yet");
+        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
+            return fail("epx_draw_diagnostics: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only",
+                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
+        a.draws = c->draws + (size_t)k0 * S * P;
+    }
+    a.k0 = k0; a.chains = chains; a.nkeep = S / chains; a.P = c->P;
+    a.d = c->d; a.pg = c->pg; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    const int n = 2 * chains * (a.nkeep / 2);
+    a.tau_min = n > 1 ? 1.0 / log10((double)n) : 0.0;
+    a.in_lds = diag_lds_doubles(chains, a.nkeep, true) * 8 + 1024 <= LDS_CAP;
+    const size_t lds = diag_lds_doubles(chains, a.nkeep, a.in_lds != 0) * 8;
+    if (set_lds(k_draw_diag, lds)) return -1;
+    const size_t nout = (size_t)count * P * EPX_DG_COUNT;
+    HIPCHK(c->diag_out.grow(nout));
+    a.out = c->diag_out;
+    hipLaunchKernelGGL(k_draw_diag, dim3((unsigned)count, (unsigned)((P + EPX_DG_TILE - 1) / EPX_DG_TILE)), dim3(256), lds,
+                       c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, a.out, nout * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (nsamp) *nsamp = n;
+    return 0;
+}
+
 int epx_pooled_moments(epx_ctx *c, int k0, int count, const double *center, const double *theta, int S, int want_scatter,
                        double *sum, double *scatter, long long *n) {
     CTX(c);

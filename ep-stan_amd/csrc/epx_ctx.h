@@ -107,8 +107,9 @@ struct epx_ctx {
     DevBuf<double> pooled_ws;       // epx_pooled_moments: [partial tiles | partial sums | scatter | sum | centre]
     DevBuf<double> pred_ws;         // epx_predict: [new rows (n x D) | responses (n) | results (n x EPX_PR_COUNT)]
     DevBuf<int> pred_iws;           // ... [workgroup records (4 ints each) | sorted position -> row (n)]
+    DevBuf<double> diag_out;        // epx_draw_diagnostics: the call's records (count x P x EPX_DG_COUNT)
     int has_last = 0;
-    int nsamp = 0;                  // draws per site of the last tilted/moments call
+    int nsamp = 0;                 // draws per site of the last tilted/moments call
     double last_df = 0.0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipStream_t stream2 = nullptr;  // second queue of a split sampling launch (epx_set_site_split)

@@ -151,6 +151,26 @@ struct PredictArgs {
 };
 __global__ void k_predict(PredictArgs a);
 
+// Per-coordinate diagnostics of the draws in device memory (draw_diag.hip; include/epx.h: epx_draw_diagnostics).  A
+// workgroup takes one site and EPX_DG_TILE coordinates; EPX_DG_SLOTS threads per coordinate share its half chains; lags
+// are computed EPX_DG_LAGS at a time.
+enum { EPX_DG_TILE = 32, EPX_DG_SLOTS = 8, EPX_DG_LAGS = 8, EPX_DG_MAX_CHAINS = 16 };
+struct DiagArgs {
+    int k0, chains, nkeep, P;          // k0: first site (absolute: indexes site_g0)
+    int d, pg;
+    const int *site_g0;                // multi-group sites: coordinates of site k = d + groups * pg (<= P); or NULL
+    int in_lds;                        // the centred tile of a site (2 chains x (nkeep / 2) draws x 32 coordinates) is kept in LDS
+    double tau_min;                    // 1 / log10(used draws): the floor of the autocorrelation time
+    const double *draws;               // site b of the call at draws + b * chains * nkeep * P: chain-major records of P
+    double *out;                       // count x P x EPX_DG_COUNT
+};
+// doubles of dynamic LDS: [slot partial sums | half-chain means | centred tile]
+constexpr size_t diag_lds_doubles(int chains, int nkeep, bool in_lds) {
+    return (size_t)EPX_DG_SLOTS * EPX_DG_LAGS * EPX_DG_TILE + (size_t)2 * chains * EPX_DG_TILE
+        + (in_lds ? (size_t)2 * chains * (nkeep / 2) * EPX_DG_TILE : 0);
+}
+__global__ void k_draw_diag(DiagArgs a);
+
 __global__ void k_cavity(CavityArgs a);
 __global__ void k_moments(MomentArgs a);
 __global__ void k_site_sums_partial(SumArgs a);

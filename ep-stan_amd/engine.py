@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from . import diagnostics as _diagnostics
 from . import site_params as _site_params
 from ._lib import SamplerOpts, check, dptr
 
@@ -543,6 +544,27 @@ class HipEngine(object):
                                    row_group.ctypes.data_as(_lib.c_int32_p) if row_group is not None else None,
                                    dptr(Xn), dptr(y), dptr(theta), int(S), dptr(out), None))
         return out
+
+    def draw_diagnostics(self, k0=0, count=None, theta=None, chains=None, with_n=False):
+        """Per-coordinate diagnostics of the draws of the sites k0..k0+count (epx_draw_diagnostics, include/epx.h):
+        (count, P, 6), columns diagnostics.DG_MEAN, DG_VAR, DG_RHAT, DG_ESS, DG_MCSE, DG_ESS_SQ; NaN behind a
+        multi-group site's own `site_P[k]` coordinates.  The draws, chains and nkeep are those of the last sampling
+        call, on the device; `theta` (count, S, P), chain-major, with `chains` injects draws instead (test hook).
+        with_n: also return the used draws per site."""
+        count = self.K - k0 if count is None else count
+        S = 0
+        if theta is not None:
+            if chains is None:
+                raise ValueError('injected draws need `chains`')
+            theta = np.ascontiguousarray(theta, dtype=np.float64)
+            if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
+                raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
+            S = theta.shape[1]
+        out = np.zeros((max(int(count), 0), self.P, _diagnostics.DG_COUNT))
+        n = ctypes.c_int()
+        check(self.lib.epx_draw_diagnostics(self.ctx, int(k0), int(count), dptr(theta), int(S),
+                                            int(chains) if theta is not None else 0, dptr(out), ctypes.byref(n)))
+        return (out, n.value) if with_n else out
 
     def pooled_moments(self, center=None, k0=0, count=None, theta=None, want_scatter=True):
         """Moments of the phi draws of the sites k0..k0+count pooled (epx_pooled_moments, include/epx.h): (n, sum, scatter)

@@ -29,6 +29,7 @@ import time
 import numpy as np
 from numpy.linalg import LinAlgError
 
+from . import diagnostics as _diagnostics
 from . import dist as _dist
 from . import engine as _engine
 from . import mix_pred as _mix_pred
@@ -259,6 +260,16 @@ class Worker(object):
         dQi[...] = dQ
         dri[...] = dr
         return ok
+
+    def diagnostics(self):
+        """Per-coordinate diagnostics of the draws of this site's last `tilted` on a stand-alone Worker's own engine:
+        the (P, DG_COUNT) record of `diagnostics.diagnostics_host` (columns DG_MEAN, DG_VAR, DG_RHAT, DG_ESS, DG_MCSE,
+        DG_ESS_SQ), computed on the device (epx_draw_diagnostics)."""
+        if self._master is not None:
+            raise RuntimeError("This site belongs to a Master: use Master.diagnostics()")
+        if not self._has_sampled:
+            raise RuntimeError("Can not diagnose draws before `tilted` has sampled some.")
+        return self._eng.draw_diagnostics(k0=self._k, count=1)[0]
 
     def _void_update(self):
         """A chain of this site started at a non-finite density (its draws are its initial point):
@@ -831,6 +842,51 @@ class Master(object):
         return dict(mean=out[:, _site_params.PR_MEAN].copy(), f_mean=out[:, _site_params.PR_F_MEAN].copy(),
                     f_var=out[:, _site_params.PR_F_M2] / (S - 1),
                     lpd=out[:, _site_params.PR_LPD].copy() if ys is not None else None, n=S)
+
+    def diagnostics(self):
+        """Per-coordinate diagnostics of the tilted draws of the last iteration (include/epx.h, enum epx_diag, states
+        the definition): which site's moments rest on few effective draws, and whether `iter` is large enough.  The
+        reference reports one number per site, the largest split-Rhat (`mrhats`); it has no counterpart.
+
+        Returns a dict.  `mean`, `var`, `rhat`, `ess`, `ess_sq`, `mcse`: each (K, Pmax), one row per site over its
+        sampled coordinates, the columns `[:dphi]` are phi, NaN behind a site's own coordinates (multi-group sites of
+        different sizes) -- the mean and the variance estimate var_plus of a coordinate, its split-Rhat, the effective
+        sample size of its mean and of its second moment (x - mean)^2, and the Monte-Carlo standard error of the
+        mean.  `n` (K): the used draws per site.  `site_max_rhat` (K): the largest Rhat of a site (NaN entries
+        skipped; NaN when all are); `site_min_ess` (K): the smallest of `ess` and `ess_sq`; `worst`: (site,
+        coordinate) of the smallest `site_min_ess`, None when there is none.
+
+        The draws stay in device memory, the kernel k_draw_diag reduces them to six numbers per coordinate; an engine
+        without `draw_diagnostics` (the CPU oracle the tests inject) hands its draws to `diagnostics.diagnostics_host`.
+        With several ranks every rank computes its own sites and the records are gathered over the communicator:
+        every rank returns the same result."""
+        if self.iter == 0:
+            raise RuntimeError("Can not diagnose draws before at least one iteration has been done.")
+        if self._draws_injected:
+            raise RuntimeError("The draws of the last iteration were injected (`_sample_injector`): they hold phi "
+                               "only, nothing can be diagnosed from them.")
+        eng, C = self.engine, _diagnostics.DG_COUNT
+        chains = int(self.workers[self.k_lo].stan_params['chains'])
+        ng_local = self._site_ng[self.k_lo:self.k_hi]
+        pg = (eng.P - eng.d) // int(ng_local.max())              # coordinates per group behind phi
+        site_P = eng.d + self._site_ng * pg                      # (K): every site's own coordinates
+        Pmax = int(site_P.max())
+        rec = np.full((Pmax * C + 1, self.K_local), np.nan, order='F')
+        if hasattr(eng, 'draw_diagnostics'):
+            loc, n = eng.draw_diagnostics(with_n=True)
+        else:
+            loc = np.full((self.K_local, eng.P, C), np.nan)
+            for j in range(self.K_local):
+                Pk = int(site_P[self.k_lo + j])
+                theta = np.ascontiguousarray(eng.get_draws(j, all_params=True))
+                loc[j, :Pk] = _diagnostics.diagnostics_host(theta[:, :Pk], chains)
+            n = 2 * chains * ((theta.shape[0] // chains) // 2)
+        for j in range(self.K_local):
+            rec[:eng.P * C, j] = loc[j].ravel()
+        rec[-1, :] = n
+        full = self.comm.allgather_sites(rec, self.K)
+        out = np.ascontiguousarray(full[:-1, :].T).reshape(self.K, Pmax, C)
+        return _diagnostics.summarise(out, np.rint(full[-1, :]).astype(np.int64))
 
     # a site whose slowest chain took more than this fraction of the iteration's slowest chain is
     # scheduled one workgroup per chain next time (measured leapfrog: 5.6 vs 10.3 us at D=32, n=500)

@@ -314,6 +314,40 @@ enum epx_pred { EPX_PR_MEAN = 0, EPX_PR_F_MEAN, EPX_PR_F_M2, EPX_PR_LPD, EPX_PR_
 int epx_predict(epx_ctx *ctx, int k0, int count, const int64_t *row_lim, const int32_t *row_group, const double *Xn,
                 const double *yn, const double *theta, int S, double *out, int *nsamp);
 
+/* Per-coordinate diagnostics of the draws of the sites k0..k0+count (no counterpart in the reference, which reports the
+ * largest split-Rhat of a site and nothing else: EPX_ST_RHAT above stays as it is).  The definition, stated once; the
+ * kernel k_draw_diag and diagnostics.diagnostics_host both follow it.  Per site and per sampled coordinate x: every chain
+ * is split into its first and its last h = nkeep / 2 draws (an odd nkeep drops the middle draw), M = 2 chains half chains
+ * of length h, n = M h used draws.  With mean_m the mean of half chain m, dev = x - mean_m (centred in a second pass) and
+ * acov_m(t) = (1/h) sum_{i < h-t} dev_i dev_{i+t}:
+ *   W        = mean_m acov_m(0) h / (h - 1)
+ *   var_plus = W (h - 1) / h + var(mean_m, ddof = 1)
+ *   rho(t)   = 1 - (W - mean_m acov_m(t)) / var_plus
+ *   EPX_DG_MEAN    mean_m mean_m;
+ *   EPX_DG_VAR     var_plus;
+ *   EPX_DG_RHAT    sqrt(var_plus / W): split-Rhat, algebraically what EPX_ST_RHAT takes the maximum of;
+ *   EPX_DG_ESS     n / tau, with Geyer's initial positive, monotone sequence over pairs of lags: pair_0 = 1 + rho(1),
+ *                  pair_j = rho(2j) + rho(2j+1) while 2j+1 < h, ended in front of the first pair that is not > 0, every
+ *                  pair replaced by the smallest pair so far, tau = -1 + 2 sum pairs, floored at 1 / log10(n).
+ *                  Antithetic chains give ESS > n: there is no cap;
+ *   EPX_DG_MCSE    sqrt(var_plus / ESS): the Monte-Carlo standard error of EPX_DG_MEAN;
+ *   EPX_DG_ESS_SQ  the ESS of z = (x - MEAN)^2 by the same procedure: how well the second moments, which the precision
+ *                  estimate is built from, are known.
+ * Results, never faults: RHAT, ESS, MCSE and ESS_SQ are NaN when nkeep < 4, when W is not a finite number > 0 (a constant
+ * coordinate, e.g. of a chain that failed at its start; any non-finite draw of the coordinate) -- MEAN and VAR are then
+ * what the arithmetic gives; chains == 1 is well defined (M = 2).
+ * out (host): count x P x EPX_DG_COUNT, P the context's record stride; the records behind a multi-group site's own P_k
+ * coordinates are NaN.  theta == NULL: the draws, chains and nkeep of the last sampling call (error "no draws yet" before
+ * one, and an error when that call did not cover every site of the range), S and chains are ignored; otherwise TEST HOOK:
+ * injected draws (count, S, P) row-major, chain-major within a site, as epx_named_moments takes them (a site reads its
+ * own coordinates of a record only), S a multiple of chains, 1 <= chains <= 16.  nsamp out (may be NULL): the used draws
+ * n per site.  A site's centred draws of 32 coordinates are kept in LDS while they fit (about 560 draws per site);
+ * longer runs read them from global memory: the same bits, slower.  No floating-point atomics: the same bits on every
+ * call.  Stream-ordered, one launch, one synchronisation. */
+enum epx_diag { EPX_DG_MEAN = 0, EPX_DG_VAR, EPX_DG_RHAT, EPX_DG_ESS, EPX_DG_MCSE, EPX_DG_ESS_SQ, EPX_DG_COUNT };
+int epx_draw_diagnostics(epx_ctx *ctx, int k0, int count, const double *theta, int S, int chains,
+                         double *out /* count * P * EPX_DG_COUNT */, int *nsamp);
+
 /* ---------------------------------------------------------------------------------------------
  * Several GPUs: sites are sharded over the ranks (one context each); the only exchange of an EP
  * iteration is the reduction of method.py:1073-1074 (Q = sum_k Qi2 + Q0 over ALL sites) and the logical
