@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -15,6 +16,7 @@
 #include "../../include/epx.h"
 #include "epx_kernels.h"
 #include "epx_pieces.h"
+#include "psis.h"
 #include "epx_ctx.h"
 
 using namespace epx;
@@ -184,6 +186,7 @@ static int ctx_create(int device, int model, int K_local, int D, const int64_t *
         }
         if (g_cnt) {
             c->g_cnt.assign(g_cnt, g_cnt + K_local);
+            c->g_lim.assign(g_lim, g_lim + gi + 1);
             c->P = d + c->ng_max * c->pg;           // record stride: the largest site
         }
     }
@@ -1321,6 +1324,94 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
     return 0;
 }
 
+// LDS of the per-row PSIS stage (psis.h): 16 rows' scratch
+static size_t psis_lds_bytes(int M) { return (size_t)16 * psis_scratch_doubles(M) * 8; }
+
+int epx_loo(epx_ctx *c, int k0, int count, const double *theta, int S, double *out, int *nsamp) {
+    CTX(c);
+    if (check_range(c, k0, count)) return -1;
+    if (c->D > EPX_PR_DMAX) return fail("epx_loo: D = %d columns, at most %d", c->D, (int)EPX_PR_DMAX);
+    if (!out) return fail("epx_loo: out is required");
+    const size_t P = c->P;
+    LooArgs a;
+    if (theta) {
+        if (S < 1) return fail("epx_loo: S = %d draws", S);
+        const size_t need = (size_t)count * S * P;
+        HIPCHK(c->inj.grow(need));
+        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
+        a.p.draws = c->inj;
+    } else {
+        S = c->s_chains * c->s_nkeep;
+        if (!c->draws || S < 1 || c->drawn_count < 1) return fail("no draws yet");
+        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
+            return fail("epx_loo: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only",
+                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
+        a.p.draws = c->draws + (size_t)k0 * S * P;
+    }
+    if (nsamp) *nsamp = S;
+    a.p.model = c->model; a.p.D = c->D; a.p.d = c->d; a.p.gauss = c->gauss; a.p.P = c->P; a.p.S = S;
+    a.p.KP = (1 + c->D + 3) / 4 * 4;
+    a.p.k0 = k0; a.p.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    a.p.perm = nullptr; a.p.y = nullptr; a.p.out = nullptr; a.p.X = c->X;
+    a.y8 = c->y; a.yd = c->yd;
+    a.M = psis_tail_length(S); a.mfit = psis_fit_points(a.M);
+    a.stride = loo_stride(S);
+    // LDS: [coefficient slab | log sigma, sigma of the slab | PSIS scratch | tiles]; the tiles go to the workspace when
+    // not even one fits
+    size_t cap = LDS_CAP - 1024;
+    if (const char *e = getenv("EPX_LOO_LDS_BYTES")) {
+        const long long v = atoll(e);
+        if (v >= 0 && (size_t)v < cap) cap = (size_t)v;
+    }
+    const size_t fixed = ((size_t)a.p.KP * 16 + 32) * 8 + psis_lds_bytes(a.M), tile = (size_t)16 * a.stride * 8;
+    if (a.mfit > PSIS_FIT_MAX || fixed > LDS_CAP - 1024)
+        return fail("epx_loo: S = %d draws: the tail of %d draws per row does not fit the LDS", S, a.M);
+    a.tiles = fixed + 4 * tile <= cap ? 4 : fixed + 2 * tile <= cap ? 2 : fixed + tile <= cap ? 1 : 0;
+    const bool in_lds = a.tiles > 0;
+    if (!in_lds) a.tiles = 1;
+    const size_t lds = fixed + (in_lds ? a.tiles * tile : 0);
+    // work items: up to 16 x tiles rows of one (site, group), in the context's row order
+    const int item = 16 * a.tiles;
+    std::vector<PredictWg> wg;
+    for (int j = 0; j < count; ++j) {
+        const int k = k0 + j, ng = c->multi ? c->g_cnt[k] : 1;
+        size_t gi = 0;
+        if (c->multi) for (int i = 0; i < k; ++i) gi += (size_t)c->g_cnt[i];
+        for (int g = 0; g < ng; ++g) {
+            const int64_t lo = c->multi ? c->g_lim[gi + g] : c->k_lim[k], hi = c->multi ? c->g_lim[gi + g + 1] : c->k_lim[k + 1];
+            for (int64_t r = lo; r < hi; r += item)
+                wg.push_back(PredictWg{j, g, (int)r, (int)(hi - r < item ? hi - r : item)});
+        }
+    }
+    if (c->N > 0x7fffffff) return fail("epx_loo: %lld rows, at most 2^31 - 1", (long long)c->N);
+    a.row0 = c->k_lim[k0];
+    const size_t rows = (size_t)(c->k_lim[k0 + count] - c->k_lim[k0]), nwg = wg.size();
+    // the grid: every item its own workgroup up to a few per compute unit (the LDS holds one or two), then they walk
+    const size_t grid_cap = (size_t)(c->n_cu > 0 ? c->n_cu : 256) * (in_lds ? 4 : 2);
+    const unsigned grid = (unsigned)(nwg < grid_cap ? nwg : grid_cap);
+    const size_t n_out = rows * EPX_LO_COUNT, n_slab = in_lds ? 0 : (size_t)grid * item * a.stride;
+    HIPCHK(c->loo_ws.grow(n_out + n_slab));
+    HIPCHK(c->pred_iws.grow(4 * nwg));
+    a.out = c->loo_ws; a.slab = in_lds ? nullptr : c->loo_ws + n_out;
+    a.nwg = (int)nwg;
+    int *wg_d = c->pred_iws;
+    if (set_lds(k_loo, lds)) return -1;
+    {
+        // `wg` is this frame's: once its copy is queued nothing returns before the stream has been synchronised
+        hipError_t e = hipMemcpyAsync(wg_d, wg.data(), nwg * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) {
+            a.p.wg = reinterpret_cast<const PredictWg *>(wg_d);
+            hipLaunchKernelGGL(k_loo, dim3(grid), dim3(256), lds, c->stream, a);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(out, a.out, n_out * 8, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream);
+        HIPCHK(e);
+        HIPCHK(es);
+    }
+    return 0;
+}
+
 int epx_draw_diagnostics(epx_ctx *c, int k0, int count, const double *theta, int S, int chains, double *out, int *nsamp) {
     CTX(c);
     if (check_range(c, k0, count)) return -1;
@@ -1659,6 +1750,31 @@ int epx_olse(int device, int d, int nb, double *S, int n, const double *P, int32
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(S, Sd, (size_t)nb * d * d * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(info, infod, nb * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int epx_psis_rows(int device, long long n, int S, const double *ll, double *out) {
+    DeviceGuard guard;
+    if (need_device(device)) return -1;
+    if (n < 0 || S < 1) return fail("epx_psis_rows: n = %lld rows of S = %d draws", n, S);
+    if (n == 0) return 0;
+    if (!ll || !out) return fail("epx_psis_rows: ll and out are required");
+    PsisRowsArgs a;
+    a.n = n; a.S = S; a.M = psis_tail_length(S); a.mfit = psis_fit_points(a.M);
+    const size_t lds = psis_lds_bytes(a.M);
+    if (a.mfit > PSIS_FIT_MAX || lds > LDS_CAP - 1024)
+        return fail("epx_psis_rows: S = %d draws: the tail of %d draws per row does not fit the LDS", S, a.M);
+    DevBuf<double> lld, outd;
+    HIPCHK(lld.alloc((size_t)n * S));
+    HIPCHK(outd.alloc((size_t)n * 3));
+    HIPCHK(hipMemcpy(lld, ll, (size_t)n * S * 8, hipMemcpyHostToDevice));
+    a.ll = lld; a.out = outd;
+    const long long steps = (n + 15) / 16;
+    if (set_lds(k_psis_rows, lds)) return -1;
+    hipLaunchKernelGGL(k_psis_rows, dim3((unsigned)(steps < 65536 ? steps : 65536)), dim3(256), lds, 0, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, outd, (size_t)n * 3 * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

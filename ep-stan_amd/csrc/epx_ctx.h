@@ -76,6 +76,7 @@ struct epx_ctx {
     std::vector<int> g_cnt;
     DevBuf<int> site_g0_d;
     DevBuf<int64_t> g_lim_d;
+    std::vector<int64_t> g_lim;     // host copy of the groups' row limits (epx_loo cuts its work items along them)
     int multi = 0, ng_max = 0, nt_max = 0, pg = 0;
     int n_max = 0;
     // device buffers
@@ -107,6 +108,7 @@ struct epx_ctx {
     DevBuf<double> pooled_ws;       // epx_pooled_moments: [partial tiles | partial sums | scatter | sum | centre]
     DevBuf<double> pred_ws;         // epx_predict: [new rows (n x D) | responses (n) | results (n x EPX_PR_COUNT)]
     DevBuf<int> pred_iws;           // ... [workgroup records (4 ints each) | sorted position -> row (n)]
+    DevBuf<double> loo_ws;          // epx_loo: [results (rows x EPX_LO_COUNT) | log-likelihood slabs, one per workgroup, when LDS is too small]
     DevBuf<double> diag_out;        // epx_draw_diagnostics: the call's records (count x P x EPX_DG_COUNT)
     int has_last = 0;
     int nsamp = 0;                 // draws per site of the last tilted/moments call

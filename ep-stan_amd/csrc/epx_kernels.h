@@ -151,6 +151,32 @@ struct PredictArgs {
 };
 __global__ void k_predict(PredictArgs a);
 
+// Leave-one-out cross-validation of the context's own rows (predict.hip: k_loo; include/epx.h: epx_loo) and the per-row
+// PSIS stage alone (k_psis_rows; epx_psis_rows); psis.h holds the per-row code and the sizes of its scratch.
+struct LooArgs {
+    PredictArgs p;                     // model, sizes, draws as k_predict takes them; X: the context's rows; wg: the work
+                                       // items (first = row of the context, rows <= 16 x tiles); perm, y, out unused
+    int nwg;                           // work items (a workgroup takes blockIdx.x, + gridDim.x, ...)
+    const uint8_t *y8;                 // responses of the Bernoulli family ...
+    const double *yd;                  // ... and of the Gaussian one
+    long long row0;                    // first row of the call: row i is written at out + (i - row0) x EPX_LO_COUNT
+    double *out;
+    int M, mfit;                       // psis_tail_length(S), psis_fit_points(M)
+    int tiles;                         // 16-row tiles (waves with rows) per work item: 4, 2 or 1
+    int stride;                        // doubles per row of the log-likelihood tile
+    double *slab;                      // NULL: the tile is in LDS; else gridDim.x slabs of 16 x tiles x stride doubles
+};
+// doubles per row of the tile: S rounded up to 16, an odd number of 16s (bank layout: predict.hip)
+constexpr int loo_stride(int S) { return ((S + 15) / 16 | 1) * 16; }
+__global__ void k_loo(LooArgs a);
+struct PsisRowsArgs {
+    long long n;
+    int S, M, mfit;
+    const double *ll;                  // n x S row-major
+    double *out;                       // n x 3: ELPD, KHAT, WESS
+};
+__global__ void k_psis_rows(PsisRowsArgs a);
+
 // Per-coordinate diagnostics of the draws in device memory (draw_diag.hip; include/epx.h: epx_draw_diagnostics).  A
 // workgroup takes one site and EPX_DG_TILE coordinates; EPX_DG_SLOTS threads per coordinate share its half chains; lags
 // are computed EPX_DG_LAGS at a time.

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib
 from . import diagnostics as _diagnostics
+from . import loo as _loo
 from . import site_params as _site_params
 from ._lib import SamplerOpts, check, dptr
 
@@ -66,6 +67,7 @@ class HipEngine(object):
         self.D = X.shape[1]
         self.d, self.P = model_dims(model if model.endswith('_sg') else model + '_sg', self.D)
         self.device = device
+        self.k_lim = k_lim
         self._trace_sites = 0                  # (set_trace: sites whose transitions are recorded; 0 = off)
         ctx = ctypes.c_void_p()
         if gauss and g_cnt is None:
@@ -543,6 +545,34 @@ class HipEngine(object):
         check(self.lib.epx_predict(self.ctx, int(k0), int(count), row_lim.ctypes.data_as(_lib.c_int64_p),
                                    row_group.ctypes.data_as(_lib.c_int32_p) if row_group is not None else None,
                                    dptr(Xn), dptr(y), dptr(theta), int(S), dptr(out), None))
+        return out
+
+    def loo(self, k0=0, count=None, theta=None, with_n=False):
+        """Leave-one-out records of the context's own rows of the sites k0..k0+count (epx_loo, include/epx.h):
+        (rows, 6), columns loo.LO_LPD, LO_LL_MEAN, LO_LL_M2, LO_ELPD, LO_KHAT, LO_WESS, in the context's row order.  The
+        draws are those of the last sampling call, on the device; `theta` (count, S, P) injects draws instead (test
+        hook).  with_n: also return the draws per site."""
+        count = self.K - k0 if count is None else count
+        S = 0
+        if theta is not None:
+            theta = np.ascontiguousarray(theta, dtype=np.float64)
+            if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
+                raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
+            S = theta.shape[1]
+        ok = 0 <= k0 and count >= 1 and k0 + count <= self.K        # (a bad range: the library says so)
+        rows = int(self.k_lim[k0 + count] - self.k_lim[k0]) if ok else 0
+        out = np.zeros((rows, _loo.LO_COUNT))
+        n = ctypes.c_int()
+        check(self.lib.epx_loo(self.ctx, int(k0), int(count), dptr(theta), int(S), dptr(out), ctypes.byref(n)))
+        return (out, n.value) if with_n else out
+
+    def psis_rows(self, ll):
+        """PSIS of every row of ll (n, S) on this engine's device (epx_psis_rows): (n, 3), columns ELPD, KHAT, WESS."""
+        ll = np.ascontiguousarray(ll, dtype=np.float64)
+        if ll.ndim != 2 or ll.shape[1] < 1:
+            raise ValueError('ll: (n, S) with S >= 1')
+        out = np.zeros((ll.shape[0], 3))
+        check(self.lib.epx_psis_rows(int(self.device), ll.shape[0], ll.shape[1], dptr(ll), dptr(out)))
         return out
 
     def draw_diagnostics(self, k0=0, count=None, theta=None, chains=None, with_n=False):

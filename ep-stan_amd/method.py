@@ -32,6 +32,7 @@ from numpy.linalg import LinAlgError
 from . import diagnostics as _diagnostics
 from . import dist as _dist
 from . import engine as _engine
+from . import loo as _loo
 from . import mix_pred as _mix_pred
 from . import site_params as _site_params
 from .seeds import MAX_UINT, run_seeds, stan_seed, stan_seeds
@@ -842,6 +843,70 @@ class Master(object):
         return dict(mean=out[:, _site_params.PR_MEAN].copy(), f_mean=out[:, _site_params.PR_F_MEAN].copy(),
                     f_var=out[:, _site_params.PR_F_M2] / (S - 1),
                     lpd=out[:, _site_params.PR_LPD].copy() if ys is not None else None, n=S)
+
+    def _local_loo(self):
+        """Leave-one-out records (rows of this rank's sites, 6) and the draws per site (see HipEngine.loo).  The device
+        engine computes them next to the draws; an engine without `loo` (the CPU oracle the tests inject) hands its
+        draws to loo.loo_host."""
+        eng = self.engine
+        if hasattr(eng, 'loo'):
+            return eng.loo(with_n=True)
+        mid, gauss, sg = self._site_spec()
+        r0 = int(self.k_lim[self.k_lo])
+        out = np.zeros((int(self.k_lim[self.k_hi]) - r0, _loo.LO_COUNT))
+        j_ind = None if sg else np.asarray(self.A_n['j_ind'])
+        S = 0
+        for j in range(self.K_local):
+            lo, hi = int(self.k_lim[self.k_lo + j]), int(self.k_lim[self.k_lo + j + 1])
+            theta = eng.get_draws(j, all_params=True)
+            S = theta.shape[0]
+            out[lo - r0:hi - r0] = _loo.loo_host(mid, self.D, int(self._site_ng[self.k_lo + j]), gauss, theta,
+                                                 self.X[lo:hi], None if sg else j_ind[lo:hi] - 1, self.y[lo:hi])
+        return out, S
+
+    def loo(self):
+        """Leave-one-out cross-validation of the fitted site models on the rows they were fitted to, from the tilted
+        draws of the last iteration: PSIS-LOO with the Pareto k-hat diagnostic, and WAIC (include/epx.h, enum epx_loo,
+        states the definition; the reference has no counterpart).  The number that compares `m1b` ... `m5b` (or the
+        `a` family) on the same data: `predict(X, ..., y_new=y)` gives the in-sample log predictive density, which
+        always flatters the larger model.
+
+        What the number means here: the draws of a site come from its TILTED distribution, the cavity (all other
+        sites' approximations and the prior) times the site's own likelihood -- EP's approximation of the posterior of
+        that site's parameters.  Row i of site k is held out by importance-weighting the draws of site k with
+        1 / p(y_i | draw); the other sites enter through the cavity, which is kept as it is.  The leave-one-out is
+        therefore CONDITIONAL on the EP approximation: it is the exact LOO of the model only as far as the tilted
+        distributions are the exact posterior marginals, and it does not propagate the removal of a row into the
+        shared parameters' cavity.  A k-hat above the threshold says that the importance weights of that row are too
+        heavy-tailed for its estimate to be trusted at this number of draws.
+
+        Returns the dict of `loo.summarise`: the totals `elpd_loo`, `p_loo`, `elpd_waic`, `p_waic` with their standard
+        errors `se_*`, the pointwise arrays `lpd`, `elpd_loo_i`, `p_loo_i`, `elpd_waic_i`, `p_waic_i`, `khat`, `wess`,
+        `ll_mean` (N each, in the order of the Master's rows: by site), the per-site sums `site_*` (K each), `n` the
+        draws per site, `khat_threshold`, `n_bad` and `worst`.
+
+        The draws stay in device memory: the kernel k_loo forms every row's log-likelihoods under its site's draws
+        on the matrix pipe, keeps them on chip and reduces them to six numbers per row.  With several ranks every
+        rank computes the rows of its own sites and one all-reduce makes every rank return the same result."""
+        if self.iter == 0:
+            raise RuntimeError("Can not cross-validate before at least one iteration has been done.")
+        if self._draws_injected:
+            raise RuntimeError("The draws of the last iteration were injected (`_sample_injector`): they hold phi "
+                               "only, nothing can be cross-validated from them.")
+        lo, hi = int(self.k_lim[self.k_lo]), int(self.k_lim[self.k_hi])
+        loc, S = self._local_loo()
+        rec = loc
+        if self.comm.world > 1:
+            # a sum carries neither NaN (a row with a non-finite log-likelihood) nor +inf (KHAT of a row that was not
+            # smoothed) next to the other ranks' zeros: they travel as a code beside the (N, 6) records
+            both = np.zeros((self.N, 2 * _loo.LO_COUNT))
+            both[lo:hi, :_loo.LO_COUNT] = np.where(np.isfinite(loc), loc, 0.0)
+            both[lo:hi, _loo.LO_COUNT:] = np.where(np.isnan(loc), 1.0, np.where(loc == np.inf, 2.0,
+                                                                                 np.where(loc == -np.inf, 3.0, 0.0)))
+            both = self.comm.allreduce_sum(both)
+            rec, code = both[:, :_loo.LO_COUNT], both[:, _loo.LO_COUNT:]
+            rec = np.where(code == 1.0, np.nan, np.where(code == 2.0, np.inf, np.where(code == 3.0, -np.inf, rec)))
+        return _loo.summarise(rec, S, self.k_lim)
 
     def diagnostics(self):
         """Per-coordinate diagnostics of the tilted draws of the last iteration (include/epx.h, enum epx_diag, states

@@ -129,16 +129,9 @@ def named_moments_host(model_id, D, ng, gauss, single_group, theta, wanted):
 PR_MEAN, PR_F_MEAN, PR_F_M2, PR_LPD, PR_COUNT = 0, 1, 2, 3, 4
 
 
-def predict_host(model_id, D, ng, gauss, theta, Xn, group, y=None):
-    """Posterior predictive of the new rows Xn (n, D) of ONE site from its draws theta (S, P) with NumPy: (n, 4),
-    columns PR_MEAN, PR_F_MEAN, PR_F_M2, PR_LPD.  group (n): 0-based group of every row within the site (None: 0).
-    With f_si = alpha_g(s) + x_i . beta_g(s), alpha and beta as `named_draws` forms them:
-      MEAN  the mean over the draws of sigmoid(f) (Bernoulli-logit models) or of f (Gaussian models);
-      F_MEAN, F_M2  the mean of f and the centred sum of squares sum_s (f_si - F_MEAN)^2;
-      LPD  log mean_s exp(ll_si), ll = y f - log(1 + e^f) or the log density of normal(f, exp(phi[0])) at y, taken
-           about the row's largest ll; NaN without y.
-    What the device kernel k_predict (csrc/predict.hip) computes; the expectation of its tests, and `Master.predict`'s
-    route on an engine without `predict`."""
+def linear_predictor(model_id, D, ng, gauss, theta, Xn, group):
+    """f (S, n): f_si = alpha_g(s) + x_i . beta_g(s) of the rows Xn (n, D) of ONE site under its draws theta (S, P),
+    alpha and beta as `named_draws` forms them.  group (n): 0-based group of every row within the site (None: 0)."""
     theta = np.asarray(theta, dtype=np.float64)
     Xn = np.asarray(Xn, dtype=np.float64).reshape(-1, D)
     n, S = Xn.shape[0], theta.shape[0]
@@ -152,24 +145,44 @@ def predict_host(model_id, D, ng, gauss, theta, Xn, group, y=None):
         rows = np.nonzero(group == g)[0]
         bg = beta if beta.ndim == 2 else beta[:, g, :]
         f[:, rows] = alpha[:, g][:, None] + bg.dot(Xn[rows].T)
+    return f
+
+
+def loglik_of(gauss, theta, f, y):
+    """ll (S, n) of the responses y (n) at the linear predictors f (S, n): y f - log(1 + e^f) (Bernoulli-logit models) or
+    the log density of normal(f, exp(phi[0])) at y (Gaussian models, theta (S, P) the draws)."""
+    y = np.asarray(y, dtype=np.float64)
+    if gauss:
+        ls = np.asarray(theta, dtype=np.float64)[:, 0][:, None]
+        return -0.5 * np.log(2 * np.pi) - ls - 0.5 * np.square((y - f) / np.exp(ls))
+    return y * f - (np.maximum(f, 0.0) + np.log1p(np.exp(-np.abs(f))))
+
+
+def predict_host(model_id, D, ng, gauss, theta, Xn, group, y=None):
+    """Posterior predictive of the new rows Xn (n, D) of ONE site from its draws theta (S, P) with NumPy: (n, 4),
+    columns PR_MEAN, PR_F_MEAN, PR_F_M2, PR_LPD.  group (n): 0-based group of every row within the site (None: 0).
+    With f_si = alpha_g(s) + x_i . beta_g(s), alpha and beta as `named_draws` forms them:
+      MEAN  the mean over the draws of sigmoid(f) (Bernoulli-logit models) or of f (Gaussian models);
+      F_MEAN, F_M2  the mean of f and the centred sum of squares sum_s (f_si - F_MEAN)^2;
+      LPD  log mean_s exp(ll_si), ll = y f - log(1 + e^f) or the log density of normal(f, exp(phi[0])) at y, taken
+           about the row's largest ll; NaN without y.
+    What the device kernel k_predict (csrc/predict.hip) computes; the expectation of its tests, and `Master.predict`'s
+    route on an engine without `predict`."""
+    f = linear_predictor(model_id, D, ng, gauss, theta, Xn, group)
+    n = f.shape[1]
     out = np.full((n, PR_COUNT), np.nan)
     if n == 0:
         return out
     fm = f.mean(axis=0)
     out[:, PR_F_MEAN] = fm
     out[:, PR_F_M2] = np.square(f - fm).sum(axis=0)
-    ll = None
     if gauss:
         out[:, PR_MEAN] = fm
-        if y is not None:
-            ls = theta[:, 0][:, None]
-            ll = -0.5 * np.log(2 * np.pi) - ls - 0.5 * np.square((np.asarray(y, dtype=np.float64) - f) / np.exp(ls))
     else:
         e = np.exp(-np.abs(f))
         out[:, PR_MEAN] = np.where(f >= 0, 1.0 / (1.0 + e), e / (1.0 + e)).mean(axis=0)
-        if y is not None:
-            ll = np.asarray(y, dtype=np.float64) * f - (np.maximum(f, 0.0) + np.log1p(e))
-    if ll is not None:
+    if y is not None:
+        ll = loglik_of(gauss, theta, f, y)
         top = ll.max(axis=0)
         out[:, PR_LPD] = top + np.log(np.exp(ll - top).mean(axis=0))
     return out

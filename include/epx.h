@@ -314,6 +314,51 @@ enum epx_pred { EPX_PR_MEAN = 0, EPX_PR_F_MEAN, EPX_PR_F_M2, EPX_PR_LPD, EPX_PR_
 int epx_predict(epx_ctx *ctx, int k0, int count, const int64_t *row_lim, const int32_t *row_group, const double *Xn,
                 const double *yn, const double *theta, int S, double *out, int *nsamp);
 
+/* Leave-one-out cross-validation of the context's OWN rows from the draws of the sites k0..k0+count: PSIS-LOO (Pareto-
+ * smoothed importance sampling) with its Pareto k-hat diagnostic, and what WAIC needs (no counterpart in the reference).
+ * The definition, stated once; the kernels k_loo / k_psis_rows (csrc/predict.hip, csrc/psis.h) and loo.psis_host /
+ * loo.loo_host both follow it.  For a training row i of site k, ll_s is the log-likelihood of its response under draw s of
+ * that site: EPX_PR_LPD's ll, with f_si = alpha_g(s) + x_i . beta_g(s), alpha and beta as EPX_NM_ALPHA / EPX_NM_BETA form
+ * them, ll = y f - log(1 + e^f) or the logarithm of the normal density of y at mean f and scale sigma = exp(phi_s[0]).
+ * Per row, over the site's S draws:
+ *   EPX_LO_LPD      log (1/S) sum_s exp(ll_s), a log-mean-exp about the largest term: EPX_PR_LPD of the row;
+ *   EPX_LO_LL_MEAN  (1/S) sum_s ll_s;
+ *   EPX_LO_LL_M2    sum_s (ll_s - LL_MEAN)^2, centred, in a second pass (the row's WAIC penalty is LL_M2 / (S - 1));
+ *   EPX_LO_ELPD, EPX_LO_KHAT, EPX_LO_WESS   PSIS:
+ *     1. lr_s = -ll_s - max_s(-ll_s): the largest is 0.
+ *     2. M = min(floor(S / 5), ceil(3 sqrt(S))).
+ *     3. The draws are ordered by (lr_s, s) ascending (ties go by draw index); the tail is the last M, u the value in
+ *        front of it.
+ *     4. Excesses x_j = exp(lr_tail_j) - exp(u), j = 1..M, ascending.
+ *     5. If M >= 5, x_q > 0 with q = floor(M / 4 + 0.5) (1-based) and x_M > x_q, a generalised Pareto distribution is
+ *        fitted by Zhang & Stephens: m = 30 + floor(sqrt(M)); b_i = 1 / x_M + (1 - sqrt(m / (i - 0.5))) / (3 x_q),
+ *        i = 1..m; k_i = mean_j log1p(-b_i x_j); L_i = M (log(-b_i / k_i) - k_i - 1); w_i = 1 / sum_j exp(L_j - L_i);
+ *        b = sum_i b_i w_i; k = mean_j log1p(-b x_j); sigma = -k / b; KHAT = (M k + 5) / (M + 10) (the weakly
+ *        informative prior: ten pseudo-observations at 0.5).
+ *     6. If KHAT is finite, the tail's lr are replaced in rank order by min(0, log(exp(u) + q_j)),
+ *        q_j = (sigma / KHAT) expm1(-KHAT log1p(-p_j)), p_j = (j - 0.5) / M; at KHAT = 0, q_j = -sigma log1p(-p_j).
+ *     7. lw = lr - logsumexp(lr).
+ *     8. ELPD = logsumexp(lw + ll).
+ *     9. WESS = 1 / sum_s exp(2 lw_s).
+ * Results, never faults: when a condition of step 5 fails or KHAT comes out non-finite nothing is smoothed, KHAT = +inf
+ * and ELPD, WESS come from the raw ratios; a row with any non-finite ll_s has NaN in all six; S = 1 gives LL_M2 = 0.
+ * out (host): rows x EPX_LO_COUNT row-major for the rows k_lim[k0] .. k_lim[k0 + count] in the context's row order.  The
+ * rows, the responses and the group limits are the context's: nothing is uploaded but the work list.  theta == NULL: the
+ * draws of the last sampling call (error "no draws yet" before one, and an error when that call did not cover every site
+ * of the range), S is ignored; otherwise TEST HOOK: injected draws (count, S, P) row-major as epx_named_moments takes
+ * them (a site reads its own coordinates of a record only).  nsamp out (may be NULL): draws per site.  At most D = 128
+ * columns.  A tile's 16 x S log-likelihoods are kept in LDS while they fit (about 900 draws at D = 32; the environment variable
+ * EPX_LOO_LDS_BYTES lowers the budget, for A/B runs and tests); longer runs keep them in a workspace sized by the grid:
+ * the same bits.  The tail, its candidates and the fit need about 16 (2.5 M + 106) doubles of LDS: an S beyond that (about 20000) is an error.  No
+ * floating-point atomics: the same bits on every call.  Stream-ordered, one launch, one synchronisation. */
+enum epx_loo { EPX_LO_LPD = 0, EPX_LO_LL_MEAN, EPX_LO_LL_M2, EPX_LO_ELPD, EPX_LO_KHAT, EPX_LO_WESS, EPX_LO_COUNT };
+int epx_loo(epx_ctx *ctx, int k0, int count, const double *theta, int S, double *out /* rows x EPX_LO_COUNT */, int *nsamp);
+
+/* The PSIS stage alone (steps 1..9 above, the same device code) on log-likelihoods the caller gives: ll (n x S row-major,
+ * host) -> out (n x 3, host: ELPD, KHAT, WESS); NaN in all three for a row with a non-finite entry.  Needs no context and
+ * leaves the calling thread's current device as it found it. */
+int epx_psis_rows(int device, long long n, int S, const double *ll, double *out /* n x 3 */);
+
 /* Per-coordinate diagnostics of the draws of the sites k0..k0+count (no counterpart in the reference, which reports the
  * largest split-Rhat of a site and nothing else: EPX_ST_RHAT above stays as it is).  The definition, stated once; the
  * kernel k_draw_diag and diagnostics.diagnostics_host both follow it.  Per site and per sampled coordinate x: every chain
