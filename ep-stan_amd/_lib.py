@@ -88,6 +88,12 @@ SIGNATURES = {
     'epx_named_len': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int_p]),
     'epx_named_moments': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int32_p, ctypes.c_int,
                                          c_double_p, ctypes.c_int, c_double_p, c_double_p, c_int_p]),
+    'epx_named_order_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int32_p, ctypes.c_int, c_int64_p,
+                                             ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_int_p]),
+    'epx_pooled_count_pass': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int32_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, c_double_p, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),
+                                             ctypes.POINTER(ctypes.c_longlong)]),
     'epx_pooled_moments': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int,
                                           ctypes.c_int, c_double_p, c_double_p, ctypes.POINTER(ctypes.c_longlong)]),
     'epx_predict': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int64_p, c_int32_p, c_double_p, c_double_p,

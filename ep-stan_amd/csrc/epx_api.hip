@@ -1234,6 +1234,146 @@ int epx_named_moments(epx_ctx *c, int k0, int count, const int32_t *names, int n
     return 0;
 }
 
+// the names, sizes and draws of a call over named parameters (epx_named_order_stats, epx_pooled_count_pass), by the rules
+// of epx_named_moments; S: in, the injected draws per site; out, the draws per site
+static int named_call_args(epx_ctx *c, const char *who, int k0, int count, const int32_t *names, int n_names,
+                           const double *theta, int *S, NamedArgs &a) {
+    if (!names || n_names < 1 || n_names > EPX_NM_MAX_REQ) return fail("%s: between 1 and %d names", who, (int)EPX_NM_MAX_REQ);
+    a.model = c->model; a.D = c->D; a.d = c->d; a.gauss = c->gauss; a.P = c->P;
+    a.ng_max = c->ng_max; a.k0 = k0; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    a.n_names = n_names; a.off[0] = 0;
+    for (int i = 0; i < n_names; ++i) {
+        const int n = named_len(names[i], a.model, a.D, a.d, a.gauss, a.ng_max);
+        if (n < 0) return fail("named parameter %d is not defined by this site model", (int)names[i]);
+        a.name[i] = names[i]; a.off[i + 1] = a.off[i] + n;
+    }
+    for (int i = n_names; i < EPX_NM_MAX_REQ; ++i) { a.name[i] = 0; a.off[i + 1] = a.off[n_names]; }
+    a.L = a.off[n_names];
+    a.mean = a.m2 = nullptr;
+    const size_t P = c->P;
+    if (theta) {
+        if (*S < 1) return fail("%s: S = %d draws", who, *S);
+        const size_t need = (size_t)count * *S * P;
+        HIPCHK(c->inj.grow(need));
+        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
+        a.draws = c->inj;
+    } else {
+        *S = c->s_chains * c->s_nkeep;
+        if (!c->draws || *S < 1 || c->drawn_count < 1) return fail("no draws yet");
+        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
+            return fail("%s: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only", who,
+                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
+        a.draws = c->draws + (size_t)k0 * *S * P;
+    }
+    a.S = *S;
+    return 0;
+}
+
+int epx_named_order_stats(epx_ctx *c, int k0, int count, const int32_t *names, int n_names, const int64_t *ranks,
+                          int n_ranks, const double *theta, int S, double *out, int *nsamp) {
+    CTX(c);
+    if (check_range(c, k0, count)) return -1;
+    if (!out) return fail("epx_named_order_stats: out is required");
+    if (!ranks || n_ranks < 1 || n_ranks > EPX_QT_MAX_RANKS)
+        return fail("epx_named_order_stats: between 1 and %d ranks (got %d)", (int)EPX_QT_MAX_RANKS, n_ranks);
+    // everything that can be refused is refused in front of the first copy: S is known without the draws
+    const int S_call = theta ? S : c->s_chains * c->s_nkeep;
+    if (theta && S < 1) return fail("epx_named_order_stats: S = %d draws", S);
+    if (S_call > order_max_draws())
+        return fail("epx_named_order_stats: S = %d draws per site, at most %d (a site's keys, padded to a power of two, are "
+                    "sorted in LDS)", S_call, order_max_draws());
+    if (theta || (c->draws && S_call >= 1 && c->drawn_count >= 1))
+        for (int i = 0; i < n_ranks; ++i) {
+            if (ranks[i] < 0 || ranks[i] >= S_call)
+                return fail("epx_named_order_stats: rank %lld outside [0, %d), the draws per site", (long long)ranks[i], S_call);
+            if (i > 0 && ranks[i] <= ranks[i - 1]) return fail("epx_named_order_stats: the ranks have to be ascending and distinct");
+        }
+    OrderArgs a;
+    if (named_call_args(c, "epx_named_order_stats", k0, count, names, n_names, theta, &S, a.nm)) return -1;
+    if ((long long)count * a.nm.L > 0x7fffffffLL) {
+        (void)hipStreamSynchronize(c->stream);            // (a copy of injected draws may be queued: it ends before the caller has the array back)
+        return fail("epx_named_order_stats: %d sites x %d elements in one call, at most 2^31 - 1", count, a.nm.L);
+    }
+    a.n_ranks = n_ranks;
+    for (int i = 0; i < EPX_QT_MAX_RANKS; ++i) a.rank[i] = i < n_ranks ? (int)ranks[i] : 0;
+    a.npad = 2;
+    while (a.npad < S) a.npad *= 2;
+    const size_t lds = (size_t)a.npad * 8, nout = (size_t)count * a.nm.L * n_ranks;
+    if (set_lds(k_site_order_stats, lds)) return -1;
+    HIPCHK(c->order_out.grow(nout));
+    a.out = c->order_out;
+    hipLaunchKernelGGL(k_site_order_stats, dim3((unsigned)(count * a.nm.L)), dim3(EPX_QT_THREADS), lds, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, a.out, nout * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (nsamp) *nsamp = S;
+    return 0;
+}
+
+int epx_pooled_count_pass(epx_ctx *c, int k0, int count, const int32_t *names, int n_names, int shift,
+                          const uint64_t *prefix, int n_targets, const double *theta, int S, long long *hist,
+                          long long *n_nan, long long *n) {
+    CTX(c);
+    if (check_range(c, k0, count)) return -1;
+    if (!hist || !n_nan || !n) return fail("epx_pooled_count_pass: hist, n_nan and n are required");
+    if (shift < 0 || shift > 56 || shift % 8 != 0) return fail("epx_pooled_count_pass: shift = %d, one of 56, 48, ..., 0", shift);
+    if (n_targets < 1 || n_targets > EPX_QT_MAX_RANKS)
+        return fail("epx_pooled_count_pass: between 1 and %d targets (got %d)", (int)EPX_QT_MAX_RANKS, n_targets);
+    if (shift < 56 && !prefix) return fail("epx_pooled_count_pass: a pass below shift 56 needs the prefixes");
+    // every site of the range holds the same elements: equal lengths of every name
+    const int ng0 = c->multi ? c->g_cnt[k0] : 1;
+    for (int i = 0; names && i < n_names && i < EPX_NM_MAX_REQ; ++i) {
+        const int l0 = named_len(names[i], c->model, c->D, c->d, c->gauss, ng0);
+        for (int k = k0 + 1; k < k0 + count; ++k) {
+            const int lk = named_len(names[i], c->model, c->D, c->d, c->gauss, c->multi ? c->g_cnt[k] : 1);
+            if (lk != l0)
+                return fail("epx_pooled_count_pass: named parameter %d has %d elements at site %d and %d at site %d: a pool "
+                            "needs equal lengths", (int)names[i], l0, k0, lk, k);
+        }
+    }
+    CountArgs a;
+    if (named_call_args(c, "epx_pooled_count_pass", k0, count, names, n_names, theta, &S, a.nm)) return -1;
+    // the row of the pool is sized by the sites of the RANGE (all alike), not by the context's largest site
+    a.nm.off[0] = 0;
+    for (int i = 0; i < n_names; ++i) a.nm.off[i + 1] = a.nm.off[i] + named_len(names[i], a.nm.model, a.nm.D, a.nm.d, a.nm.gauss, ng0);
+    for (int i = n_names; i < EPX_NM_MAX_REQ; ++i) a.nm.off[i + 1] = a.nm.off[n_names];
+    a.nm.L = a.nm.off[n_names];
+    const size_t L = (size_t)a.nm.L, nt = (size_t)n_targets;
+    a.ng = ng0; a.shift = shift; a.n_targets = n_targets;
+    a.n = (long long)count * S;
+    a.tile = EPX_QT_MAX_TILE;
+    while (a.tile > 1 && (count_lds_bytes(a.tile, n_targets) > EPX_QT_COUNT_LDS || (size_t)a.tile / 2 >= L)) a.tile /= 2;
+    const size_t lds = count_lds_bytes(a.tile, n_targets);
+    // slabs of at least 1024 records, about 2048 workgroups in all, at most 2^20 records each (32-bit counts in LDS)
+    const long long ntile = ((long long)L + a.tile - 1) / a.tile;
+    long long nslab = (a.n + 1023) / 1024;
+    const long long cap = 2048 / ntile > 1 ? 2048 / ntile : 1;
+    if (nslab > cap) nslab = cap;
+    if (nslab < (a.n + (1 << 20) - 1) / (1 << 20)) nslab = (a.n + (1 << 20) - 1) / (1 << 20);
+    a.slab_rows = (a.n + nslab - 1) / nslab;
+    nslab = (a.n + a.slab_rows - 1) / a.slab_rows;
+    if (nslab > 65535) {
+        (void)hipStreamSynchronize(c->stream);            // (a copy of injected draws may be queued: it ends before the caller has the array back)
+        return fail("epx_pooled_count_pass: %lld draws in one call, at most 65535 x 2^20", a.n);
+    }
+    const size_t n_hist = L * nt * 256;
+    HIPCHK(c->count_ws.grow(n_hist + L + L * nt));
+    a.hist = c->count_ws; a.n_nan = a.hist + n_hist;
+    unsigned long long *prefix_d = a.n_nan + L;
+    HIPCHK(hipMemsetAsync(a.hist, 0, (n_hist + L) * 8, c->stream));
+    if (shift < 56) HIPCHK(hipMemcpyAsync(prefix_d, prefix, L * nt * 8, hipMemcpyHostToDevice, c->stream));
+    a.prefix = prefix_d;
+    if (set_lds(k_pooled_count, lds)) return -1;
+    hipLaunchKernelGGL(k_pooled_count, dim3((unsigned)ntile, (unsigned)nslab), dim3(EPX_QT_THREADS), lds, c->stream, a);
+    HIPCHK(hipGetLastError());
+    static_assert(sizeof(long long) == sizeof(unsigned long long), "counts are copied as they are");
+    HIPCHK(hipMemcpyAsync(hist, a.hist, n_hist * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(n_nan, a.n_nan, L * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n = a.n;
+    return 0;
+}
+
 int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int32_t *row_group, const double *Xn,
                 const double *yn, const double *theta, int S, double *out, int *nsamp) {
     CTX(c);

@@ -118,6 +118,37 @@ struct NamedArgs {
 };
 __global__ void k_named_moments(NamedArgs a);
 
+// Order statistics across draws (quantiles.inc; include/epx.h: "Posterior quantiles").  Per site: one workgroup per (site,
+// element) sorts the element's S keys (order_key.h) in LDS, padded to a power of two.
+enum { EPX_QT_MAX_RANKS = 32, EPX_QT_THREADS = 256, EPX_QT_MAX_TILE = 16, EPX_QT_COUNT_LDS = 48 * 1024 };
+// most draws per site whose padded keys fit the LDS: the largest power of two of 8-byte keys below lds_capacity() - 1 KiB
+constexpr int order_max_draws() {
+    int n = 1;
+    while ((size_t)2 * n * 8 <= lds_capacity() - 1024) n *= 2;
+    return n;
+}
+struct OrderArgs {
+    NamedArgs nm;                      // model, sizes, names and draws as k_named_moments takes them (mean, m2 unused)
+    int n_ranks, npad;                 // npad: S rounded up to a power of two, at least 2: keys in LDS
+    int rank[EPX_QT_MAX_RANKS];        // ascending, distinct, in [0, S)
+    double *out;                       // count x L x n_ranks
+};
+__global__ void k_site_order_stats(OrderArgs a);
+// Pooled: one counting pass of the most-significant-byte-first selection over n = sites x draws records.  A workgroup
+// takes `tile` elements (a power of two) and one slab of records; LDS: [prefixes | tile x n_targets x 256 counts | NaNs].
+struct CountArgs {
+    NamedArgs nm;                      // draws: (n, P) records; every site of the range has ng groups (equal lengths)
+    int ng, shift, n_targets, tile;
+    long long n, slab_rows;            // records of the range; records per slab (gridDim.y slabs, < 2^31 each)
+    const unsigned long long *prefix;  // L x n_targets keys; the bits below shift + 8 are ignored
+    unsigned long long *hist;          // L x n_targets x 256, zeroed by the host
+    unsigned long long *n_nan;         // L, zeroed by the host
+};
+constexpr size_t count_lds_bytes(int tile, int n_targets) {
+    return (size_t)tile * n_targets * 8 + (size_t)tile * n_targets * 256 * 4 + (size_t)tile * 4;
+}
+__global__ void k_pooled_count(CountArgs a);
+
 // Pooled moments of the first d coordinates of n = sites x draws records (pooled_moments.hip; experiment/fit.py:639-646).
 struct PooledArgs {
     int d, P, nt;                      // nt = ceil(d / 16) column tiles

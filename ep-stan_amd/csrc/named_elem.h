@@ -1,6 +1,6 @@
 // How one element of a NAMED parameter of the site models is formed from the coordinates of a draw
 // theta = [phi | eta (ng) | etb (ng x D)] (site_params.py states the same in NumPy): shared by k_named_moments
-// (named_moments.hip) and k_predict (predict.hip).
+// (named_moments.hip) with the order-statistic kernels behind it (quantiles.inc), and k_predict (predict.hip).
 #pragma once
 #include "epx_device.h"
 #include "epx_kernels.h"

@@ -90,3 +90,6 @@ k_named_moments(NamedArgs a) {
 }
 
 }  // namespace epx
+
+// k_site_order_stats, k_pooled_count: the order statistics of the same elements (Master.mix_quantiles)
+#include "quantiles.inc"

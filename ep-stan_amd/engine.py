@@ -620,6 +620,82 @@ class HipEngine(object):
                                           1 if want_scatter else 0, dptr(s), dptr(sc), ctypes.byref(n)))
         return n.value, s, sc
 
+    def _named_ids(self, names):
+        names = [names] if isinstance(names, str) else list(names)
+        for name in names:
+            if name not in _site_params.NAME_IDS:
+                raise ValueError('unknown parameter name {!r} (known: {})'.format(name, sorted(_site_params.NAME_IDS)))
+        return names, np.array([_site_params.NAME_IDS[name] for name in names], dtype=np.int32)
+
+    def _named_lens(self, ids, k):
+        """Elements of every name at site k; an undefined name fails in the library like any other error."""
+        lens = []
+        for i in ids:
+            n = ctypes.c_int()
+            check(self.lib.epx_named_len(self.ctx, int(k), int(i), ctypes.byref(n)))
+            lens.append(n.value)
+        return lens
+
+    def _injected(self, theta, count):
+        if theta is None:
+            return None, 0
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
+            raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
+        return theta, theta.shape[1]
+
+    def named_order_stats(self, names, ranks, k0=0, count=None, theta=None):
+        """Per-site order statistics of named parameters of the site model (epx_named_order_stats, include/epx.h): a list,
+        one entry per site, of {name: (len(ranks),) + per-site shape} -- x_(r) of every element's draws at that site for
+        the 0-based ranks r (ascending, distinct, below the draws per site, at most 32), NaN for an element with a NaN
+        draw.  The draws are those of the last sampling call, on the device; `theta` (count, S, P) injects draws instead
+        (test hook)."""
+        count = self.K - k0 if count is None else count
+        names, ids = self._named_ids(names)
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+        mid, gauss, sg = MODEL_IDS[self.model] % 5, is_gauss(self.model), self.model.endswith('_sg')
+        theta, S = self._injected(theta, count)
+        lens = self._named_lens(ids, int(np.argmax(self.g_cnt)) if self.g_cnt is not None else 0)
+        L, R = int(sum(lens)), int(ranks.size)
+        out = np.zeros((max(int(count), 0), L, R))
+        check(self.lib.epx_named_order_stats(self.ctx, int(k0), int(count), ids.ctypes.data_as(_lib.c_int32_p), len(names),
+                                             ranks.ctypes.data_as(_lib.c_int64_p), R, dptr(theta), int(S), dptr(out), None))
+        off = np.concatenate(([0], np.cumsum(lens)))
+        stats = []
+        for b in range(count):
+            ng = 1 if self.g_cnt is None else int(self.g_cnt[k0 + b])
+            rec = {}
+            for j, name in enumerate(names):
+                shape = _site_params.named_shape(mid, self.D, ng, gauss, sg, name)
+                size = int(np.prod(shape, dtype=np.int64))
+                rec[name] = np.ascontiguousarray(out[b, off[j]:off[j] + size].T).reshape((R,) + shape)
+            stats.append(rec)
+        return stats
+
+    def pooled_count_pass(self, names, shift, prefix, n_targets, k0=0, count=None, theta=None):
+        """One counting pass of the pooled selection over the draws of the sites k0..k0+count (epx_pooled_count_pass,
+        include/epx.h; quantiles.select_pooled runs the eight passes): (hist (L, n_targets, 256) int64, n_nan (L) int64,
+        n), L = the elements of `names` in the order given, which every site of the range has to hold alike.  prefix
+        (L, n_targets) uint64, not read at shift 56 (None).  The draws are those of the last sampling call, on the device;
+        `theta` (count, S, P) injects draws instead (test hook)."""
+        count = self.K - k0 if count is None else count
+        names, ids = self._named_ids(names)
+        theta, S = self._injected(theta, count)
+        L, T = int(sum(self._named_lens(ids, k0))), int(n_targets)
+        if prefix is not None:
+            prefix = np.ascontiguousarray(prefix, dtype=np.uint64)
+            if prefix.shape != (L, T):
+                raise ValueError('prefix: (L, n_targets) = ({}, {})'.format(L, T))
+        hist = np.zeros((L, max(T, 0), 256), dtype=np.int64)
+        n_nan = np.zeros(L, dtype=np.int64)
+        n = ctypes.c_longlong()
+        ll_p = ctypes.POINTER(ctypes.c_longlong)
+        check(self.lib.epx_pooled_count_pass(
+            self.ctx, int(k0), int(count), ids.ctypes.data_as(_lib.c_int32_p), len(names), int(shift),
+            prefix.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if prefix is not None else None, T, dptr(theta), int(S),
+            hist.ctypes.data_as(ll_p), n_nan.ctypes.data_as(ll_p), ctypes.byref(n)))
+        return hist, n_nan, n.value
+
     def accept(self, df):
         check(self.lib.epx_accept(self.ctx, float(df)))
 

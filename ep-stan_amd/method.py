@@ -34,6 +34,7 @@ from . import dist as _dist
 from . import engine as _engine
 from . import loo as _loo
 from . import mix_pred as _mix_pred
+from . import quantiles as _quantiles
 from . import site_params as _site_params
 from .seeds import MAX_UINT, run_seeds, stan_seed, stan_seeds
 from .util import invert_normal_params
@@ -740,6 +741,147 @@ class Master(object):
         if only_one_param:
             return mean[0], var[0]
         return mean, var
+
+    def _local_named_draws(self, names, j):
+        """{name: draws} of local site j through site_params.named_draws (the host route of an engine without the
+        device methods)."""
+        mid, gauss, sg = self._site_spec()
+        theta = np.ascontiguousarray(self.engine.get_draws(j, all_params=True))
+        return _site_params.named_draws(mid, self.D, int(self._site_ng[self.k_lo + j]), gauss, sg, theta, names)
+
+    def _pooled_order_stats(self, names, shapes, ranks):
+        """{name: (len(ranks),) + shape}: order statistics of the pool of ALL sites' draws of parameters every site holds,
+        selected by counting over all ranks (quantiles.select_pooled)."""
+        eng, T = self.engine, len(ranks)
+        if hasattr(eng, 'pooled_count_pass'):
+            def count_pass(shift, prefix):
+                return eng.pooled_count_pass(names, shift, prefix, T)
+        else:
+            x = np.concatenate([np.concatenate([d[name].reshape(d[name].shape[0], -1) for name in names], axis=1)
+                                for d in (self._local_named_draws(names, j) for j in range(self.K_local))])
+
+            def count_pass(shift, prefix):
+                return _quantiles.count_pass_host(x, shift, prefix, T)
+        values, _, _ = _quantiles.select_pooled(count_pass, self.comm.allreduce_sum, ranks)
+        out, at = {}, 0
+        for name, sh in zip(names, shapes):
+            size = int(np.prod(sh, dtype=np.int64))
+            out[name] = np.ascontiguousarray(values[at:at + size].T).reshape((T,) + tuple(sh))
+            at += size
+        return out
+
+    def _site_order_stats(self, names, ranks):
+        """Per-site order statistics of ALL sites on every rank: a list of {name: (len(ranks),) + per-site shape}.  Every
+        rank selects its own sites' (HipEngine.named_order_stats, or quantiles.site_order_stats_host on an engine
+        without it); one record per site, flattened and padded to the widest site, is gathered like the site arrays."""
+        eng, R, K = self.engine, len(ranks), self.K
+        mid, gauss, sg = self._site_spec()
+        if hasattr(eng, 'named_order_stats'):
+            local = eng.named_order_stats(names, ranks)
+        else:
+            local = [dict((name, _quantiles.order_stats(d[name], ranks)) for name in names)
+                     for d in (self._local_named_draws(names, j) for j in range(self.K_local))]
+        if self.comm.world == 1:
+            return local
+        shapes = [[_site_params.named_shape(mid, self.D, int(self._site_ng[k]), gauss, sg, name) for name in names]
+                  for k in range(K)]
+        sizes = [[int(np.prod(sh, dtype=np.int64)) for sh in row] for row in shapes]
+        W = max(sum(row) for row in sizes)
+        rec = np.zeros((R * W, self.K_local), order='F')
+        for j in range(self.K_local):
+            flat = np.concatenate([local[j][name].reshape(R, -1) for name in names], axis=1)      # (R, the site's elements)
+            rec[:, j].reshape(R, W)[:, :flat.shape[1]] = flat
+        full = self.comm.allgather_sites(rec, K)
+        stats = []
+        for k in range(K):
+            row, d, at = np.ascontiguousarray(full[:, k]).reshape(R, W), {}, 0
+            for name, sh, size in zip(names, shapes[k], sizes[k]):
+                d[name] = row[:, at:at + size].reshape((R,) + tuple(sh))
+                at += size
+            stats.append(d)
+        return stats
+
+    def mix_quantiles(self, params, probs=(0.025, 0.25, 0.5, 0.75, 0.975), smap=None, param_shapes=None):
+        """Quantiles of named parameters of the site model from the tilted draws of the last iteration: the credible
+        intervals beside `mix_pred`'s mean and variance (include/epx.h, "Posterior quantiles", states the order of the
+        draws and the type-7 quantile, NumPy's `linear`).  The reference has no counterpart: its user extracts every draw
+        and calls np.percentile.
+
+        params, smap, param_shapes: as `mix_pred` takes them; probs: probabilities in [0, 1].  Returns, per parameter, an
+        array (len(probs),) + shape; a list of them when `params` is a list.
+
+        smap None (parameters every site holds: phi, mu_a, mu_b, sigma_a, sigma_b, sigma): the quantiles of the POOL of
+        all sites' draws, as `mix_phi` and `mix_pred` pool them.  The pool fits no chip and, with several ranks, no single
+        device: its order statistics are selected by eight counting passes (k_pooled_count), whose integer counts add
+        over the ranks exactly.  smap given: every site's own quantiles (k_site_order_stats sorts a site's draws of an
+        element in LDS), placed at the site's index; an index that no site fills and an index that several sites fill are
+        ValueErrors -- the quantile of a pool of sites is not a function of the sites' quantiles.
+
+        Only order statistics leave the device; the host interpolates (quantiles.interpolate).  An engine without the
+        device methods (the CPU oracle the tests inject) goes through the host functions of quantiles.py.  With several
+        ranks every rank returns the same result."""
+        if self.iter == 0:
+            raise RuntimeError("Can not mix samples before at least one iteration has been done.")
+        if self._draws_injected:
+            raise RuntimeError("The draws of the last iteration were injected (`_sample_injector`): they hold phi "
+                               "only, named parameters can not be mixed.")
+        only_one_param = isinstance(params, str)
+        if only_one_param:
+            params, smap, param_shapes = [params], [smap], [param_shapes]
+        params = list(params)
+        maps = [smap[ip] if smap is not None else None for ip in range(len(params))]
+        S = int(self.engine.get_tilted(0)[2])               # draws per site (the same for every site)
+        mid, gauss, sg = self._site_spec()
+        result = [None] * len(params)
+
+        pooled = [par for par, mp in zip(params, maps) if mp is None]
+        if pooled:
+            ranks, plan = _quantiles.rank_plan(S * self.K, probs)
+            shapes = []
+            for par in pooled:
+                every = set(_site_params.named_shape(mid, self.D, int(ng), gauss, sg, par) for ng in self._site_ng)
+                if len(every) != 1:
+                    raise ValueError("Without `smap` every site has to hold the whole parameter; the sites' records of "
+                                     "{!r} have the shapes {}".format(par, sorted(every)))
+                shapes.append(every.pop())
+            stats = self._pooled_order_stats(pooled, shapes, ranks)
+            for ip, par in enumerate(params):
+                if maps[ip] is None:
+                    result[ip] = _quantiles.interpolate(stats[par], ranks, plan)
+
+        mapped = [par for par, mp in zip(params, maps) if mp is not None]
+        if mapped:
+            ranks, plan = _quantiles.rank_plan(S, probs)
+            if param_shapes is None or any(param_shapes[ip] is None for ip in range(len(params)) if maps[ip] is not None):
+                raise ValueError("Arg. `param_shapes` has to be given with `smap`")
+            stats = self._site_order_stats(mapped, ranks)
+            for ip, par in enumerate(params):
+                mp = maps[ip]
+                if mp is None:
+                    continue
+                if len(mp) != self.K:
+                    raise ValueError("Arg. `smap` of {!r} needs one index per site ({}), it has {}".format(
+                        par, self.K, len(mp)))
+                filled = np.zeros(param_shapes[ip], dtype=np.int64)
+                shape = filled.shape
+                q = np.full((len(plan),) + shape, np.nan)
+                for k in range(self.K):
+                    qk = _quantiles.interpolate(stats[k][par], ranks, plan)
+                    if qk.shape[1:] != np.shape(filled[mp[k]]):
+                        raise ValueError("The record of site {} has shape {}, its map addresses {} of the parameter {}"
+                                         .format(k, qk.shape[1:], np.shape(filled[mp[k]]), shape))
+                    filled[mp[k]] += 1
+                    for ir in range(len(plan)):
+                        q[ir][mp[k]] = qk[ir]
+                if np.any(filled == 0):
+                    raise ValueError("Arg. `smap` does not fill the parameter {!r}".format(par))
+                if np.any(filled > 1):
+                    raise ValueError("Arg. `smap` lets several sites fill one index of {!r}: the quantile of a pool of "
+                                     "sites is not a function of the sites' quantiles".format(par))
+                result[ip] = q
+        if only_one_param:
+            return result[0]
+        return result
 
     def _local_predict(self, Xn, row_lim, group, y):
         """Prediction records (n_local, 4) of new rows of this rank's sites (see HipEngine.predict).  The device engine

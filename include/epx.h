@@ -393,6 +393,49 @@ enum epx_diag { EPX_DG_MEAN = 0, EPX_DG_VAR, EPX_DG_RHAT, EPX_DG_ESS, EPX_DG_MCS
 int epx_draw_diagnostics(epx_ctx *ctx, int k0, int count, const double *theta, int S, int chains,
                          double *out /* count * P * EPX_DG_COUNT */, int *nsamp);
 
+/* Posterior quantiles: order statistics across the draws, per site and over the pool of several sites (no counterpart in
+ * the reference, whose user calls `fit.extract` and np.percentile on the host).  The definition, stated once; the kernels
+ * k_site_order_stats / k_pooled_count (csrc/quantiles.inc, csrc/order_key.h) and the host restatement (quantiles.py) both
+ * follow it.
+ *   Order.  The draws x_0 .. x_{n-1} of one element are ordered by the key k(x): the IEEE-754 bits of x as uint64, all bits
+ *     flipped if the sign bit is set, otherwise the sign bit set -- so -inf < ... < -0.0 < +0.0 < ... < +inf.  x_(r) is the
+ *     value whose key has rank r ascending, 0-based; ties are the same bits, so their order does not matter.
+ *   Quantile at probability p in [0, 1] (Hyndman-Fan type 7, NumPy's `linear`).  n = 1: x_(0).  Otherwise h = p (n - 1),
+ *     i = min(floor(h), n - 2), g = h - i and q = x_(i) + g (x_(i+1) - x_(i)), evaluated in exactly that form in double
+ *     (the library is built with -ffp-contract=off).  The HOST interpolates (quantiles.interpolate) in both routes: the
+ *     device delivers order statistics, not interpolated values.
+ *   Results, never faults: an element with any NaN draw has NaN at every rank and probability, that element alone; +-inf
+ *     are ordered like any value and the interpolation gives what the arithmetic gives; a p outside [0, 1] or NaN is an
+ *     argument error (quantiles.rank_plan).
+ *
+ * Per site: out[(site, element, rank)] = x_(ranks[rank]) of the element's draws at that site, count x L x n_ranks row-major,
+ * L laid out as epx_named_moments lays it out (the names in the order given, at most 16, each padded to the context's
+ * LARGEST site) with NaN behind a site's own elements.  ranks: ascending, distinct, in [0, draws per site), at most 32.
+ * theta == NULL: the draws of the last sampling call (error "no draws yet" before one, and an error when that call did not
+ * cover every site of the range), S is ignored; otherwise TEST HOOK: injected draws (count, S, P) row-major as
+ * epx_named_moments takes them.  nsamp out (may be NULL): draws per site.  One workgroup per (site, element) sorts the
+ * element's keys in LDS, padded to a power of two with the all-ones key (a bitonic network): at most 16384 draws per site
+ * (128 KiB of keys in the 160 KiB of LDS); more is an error.  No floating-point atomics, no atomics at all: the same bits
+ * on every call.  Stream-ordered, one launch, one synchronisation. */
+int epx_named_order_stats(epx_ctx *ctx, int k0, int count, const int32_t *names, int n_names,
+                          const int64_t *ranks, int n_ranks, const double *theta, int S,
+                          double *out /* count x L x n_ranks */, int *nsamp);
+/* Pooled: ONE counting pass of the selection, most significant byte first, among the draws of the sites k0..k0+count taken
+ * together -- the posterior approximation of a parameter every site holds (phi, mu_a, mu_b, sigma_a, sigma_b, sigma), as
+ * Master.mix_phi pools them.  The pool fits no LDS and, with several ranks, no single device; counts are integers, so they
+ * add over workgroups and ranks exactly.  For every element e and target t, hist[e][t][b] = the draws of the range whose key
+ * agrees with prefix[e][t] in all bits above shift + 7 and whose byte at `shift` is b; at shift = 56 every draw counts
+ * (prefix may be NULL).  A NaN draw counts by its key like any other and is counted in n_nan[e] besides.  The caller runs the
+ * eight passes (quantiles.select_pooled): per (element, target) it walks the cumulative counts to the byte that holds the
+ * remaining rank, extends the prefix by it and reduces the rank; behind the pass at shift = 0 the prefix is the key of x_(r).
+ * L = the sum of the names' lengths at the sites of the range, which have to be equal for every name (else an error).
+ * n_targets: at most 32.  n out: the draws in the range, count x draws per site.  theta as above.  Counted in LDS
+ * histograms with integer atomics and added to the global ones with integer atomics: the same result on every call.  The
+ * workspace is the context's.  Stream-ordered, one launch, one synchronisation. */
+int epx_pooled_count_pass(epx_ctx *ctx, int k0, int count, const int32_t *names, int n_names, int shift /* 56, 48, ..., 0 */,
+                          const uint64_t *prefix /* L x n_targets */, int n_targets, const double *theta, int S,
+                          long long *hist /* L x n_targets x 256 */, long long *n_nan /* L */, long long *n);
+
 /* ---------------------------------------------------------------------------------------------
  * Several GPUs: sites are sharded over the ranks (one context each); the only exchange of an EP
  * iteration is the reduction of method.py:1073-1074 (Q = sum_k Qi2 + Q0 over ALL sites) and the logical
