@@ -18,6 +18,7 @@
 #include "epx_pieces.h"
 #include "psis.h"
 #include "epx_ctx.h"
+#include "epx_draws.h"
 
 using namespace epx;
 
@@ -1192,36 +1193,12 @@ int epx_named_moments(epx_ctx *c, int k0, int count, const int32_t *names, int n
                       double *mean, double *m2, int *nsamp) {
     CTX(c);
     if (check_range(c, k0, count)) return -1;
-    if (!names || n_names < 1 || n_names > EPX_NM_MAX_REQ)
-        return fail("epx_named_moments: between 1 and %d names", (int)EPX_NM_MAX_REQ);
     if (!mean || !m2) return fail("epx_named_moments: mean and m2 are required");
     NamedArgs a;
-    a.model = c->model; a.D = c->D; a.d = c->d; a.gauss = c->gauss; a.P = c->P;
-    a.ng_max = c->ng_max; a.k0 = k0; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
-    a.n_names = n_names; a.off[0] = 0;
-    for (int i = 0; i < n_names; ++i) {
-        const int n = named_len(names[i], a.model, a.D, a.d, a.gauss, a.ng_max);
-        if (n < 0) return fail("named parameter %d is not defined by this site model", (int)names[i]);
-        a.name[i] = names[i]; a.off[i + 1] = a.off[i] + n;
-    }
-    for (int i = n_names; i < EPX_NM_MAX_REQ; ++i) { a.name[i] = 0; a.off[i + 1] = a.off[n_names]; }
-    a.L = a.off[n_names];
-    const size_t P = c->P;
-    if (theta) {
-        if (S < 1) return fail("epx_named_moments: S = %d draws", S);
-        const size_t need = (size_t)count * S * P;
-        HIPCHK(c->inj.grow(need));
-        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
-        a.draws = c->inj;
-    } else {
-        S = c->s_chains * c->s_nkeep;
-        if (!c->draws || S < 1 || c->drawn_count < 1) return fail("no draws yet");
-        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
-            return fail("epx_named_moments: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only",
-                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
-        a.draws = c->draws + (size_t)k0 * S * P;
-    }
-    a.S = S;
+    DrawSource src;
+    if (named_front(c, "epx_named_moments", k0, count, names, n_names, theta, S, c->ng_max, a, &src)) return -1;
+    StreamSync sync{c->stream};
+    if (upload_draws(c, src, &a.draws)) return -1;
     const size_t nout = (size_t)count * a.L;
     HIPCHK(c->named_out.grow(2 * nout));
     a.mean = c->named_out; a.m2 = c->named_out + nout;
@@ -1229,44 +1206,8 @@ int epx_named_moments(epx_ctx *c, int k0, int count, const int32_t *names, int n
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(mean, a.mean, nout * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(m2, a.m2, nout * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (nsamp) *nsamp = S;
-    return 0;
-}
-
-// the names, sizes and draws of a call over named parameters (epx_named_order_stats, epx_pooled_count_pass), by the rules
-// of epx_named_moments; S: in, the injected draws per site; out, the draws per site
-static int named_call_args(epx_ctx *c, const char *who, int k0, int count, const int32_t *names, int n_names,
-                           const double *theta, int *S, NamedArgs &a) {
-    if (!names || n_names < 1 || n_names > EPX_NM_MAX_REQ) return fail("%s: between 1 and %d names", who, (int)EPX_NM_MAX_REQ);
-    a.model = c->model; a.D = c->D; a.d = c->d; a.gauss = c->gauss; a.P = c->P;
-    a.ng_max = c->ng_max; a.k0 = k0; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
-    a.n_names = n_names; a.off[0] = 0;
-    for (int i = 0; i < n_names; ++i) {
-        const int n = named_len(names[i], a.model, a.D, a.d, a.gauss, a.ng_max);
-        if (n < 0) return fail("named parameter %d is not defined by this site model", (int)names[i]);
-        a.name[i] = names[i]; a.off[i + 1] = a.off[i] + n;
-    }
-    for (int i = n_names; i < EPX_NM_MAX_REQ; ++i) { a.name[i] = 0; a.off[i + 1] = a.off[n_names]; }
-    a.L = a.off[n_names];
-    a.mean = a.m2 = nullptr;
-    const size_t P = c->P;
-    if (theta) {
-        if (*S < 1) return fail("%s: S = %d draws", who, *S);
-        const size_t need = (size_t)count * *S * P;
-        HIPCHK(c->inj.grow(need));
-        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
-        a.draws = c->inj;
-    } else {
-        *S = c->s_chains * c->s_nkeep;
-        if (!c->draws || *S < 1 || c->drawn_count < 1) return fail("no draws yet");
-        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
-            return fail("%s: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only", who,
-                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
-        a.draws = c->draws + (size_t)k0 * *S * P;
-    }
-    a.S = *S;
-    return 0;
+    if (nsamp) *nsamp = src.S;
+    return sync.finish();
 }
 
 int epx_named_order_stats(epx_ctx *c, int k0, int count, const int32_t *names, int n_names, const int64_t *ranks,
@@ -1276,38 +1217,35 @@ int epx_named_order_stats(epx_ctx *c, int k0, int count, const int32_t *names, i
     if (!out) return fail("epx_named_order_stats: out is required");
     if (!ranks || n_ranks < 1 || n_ranks > EPX_QT_MAX_RANKS)
         return fail("epx_named_order_stats: between 1 and %d ranks (got %d)", (int)EPX_QT_MAX_RANKS, n_ranks);
-    // everything that can be refused is refused in front of the first copy: S is known without the draws
-    const int S_call = theta ? S : c->s_chains * c->s_nkeep;
-    if (theta && S < 1) return fail("epx_named_order_stats: S = %d draws", S);
-    if (S_call > order_max_draws())
-        return fail("epx_named_order_stats: S = %d draws per site, at most %d (a site's keys, padded to a power of two, are "
-                    "sorted in LDS)", S_call, order_max_draws());
-    if (theta || (c->draws && S_call >= 1 && c->drawn_count >= 1))
-        for (int i = 0; i < n_ranks; ++i) {
-            if (ranks[i] < 0 || ranks[i] >= S_call)
-                return fail("epx_named_order_stats: rank %lld outside [0, %d), the draws per site", (long long)ranks[i], S_call);
-            if (i > 0 && ranks[i] <= ranks[i - 1]) return fail("epx_named_order_stats: the ranks have to be ascending and distinct");
-        }
     OrderArgs a;
-    if (named_call_args(c, "epx_named_order_stats", k0, count, names, n_names, theta, &S, a.nm)) return -1;
-    if ((long long)count * a.nm.L > 0x7fffffffLL) {
-        (void)hipStreamSynchronize(c->stream);            // (a copy of injected draws may be queued: it ends before the caller has the array back)
-        return fail("epx_named_order_stats: %d sites x %d elements in one call, at most 2^31 - 1", count, a.nm.L);
+    DrawSource src;
+    if (named_front(c, "epx_named_order_stats", k0, count, names, n_names, theta, S, c->ng_max, a.nm, &src)) return -1;
+    S = src.S;
+    if (S > order_max_draws())
+        return fail("epx_named_order_stats: S = %d draws per site, at most %d (a site's keys, padded to a power of two, are "
+                    "sorted in LDS)", S, order_max_draws());
+    for (int i = 0; i < n_ranks; ++i) {
+        if (ranks[i] < 0 || ranks[i] >= S)
+            return fail("epx_named_order_stats: rank %lld outside [0, %d), the draws per site", (long long)ranks[i], S);
+        if (i > 0 && ranks[i] <= ranks[i - 1]) return fail("epx_named_order_stats: the ranks have to be ascending and distinct");
     }
+    if ((long long)count * a.nm.L > 0x7fffffffLL)
+        return fail("epx_named_order_stats: %d sites x %d elements in one call, at most 2^31 - 1", count, a.nm.L);
     a.n_ranks = n_ranks;
     for (int i = 0; i < EPX_QT_MAX_RANKS; ++i) a.rank[i] = i < n_ranks ? (int)ranks[i] : 0;
     a.npad = 2;
     while (a.npad < S) a.npad *= 2;
     const size_t lds = (size_t)a.npad * 8, nout = (size_t)count * a.nm.L * n_ranks;
+    StreamSync sync{c->stream};
+    if (upload_draws(c, src, &a.nm.draws)) return -1;
     if (set_lds(k_site_order_stats, lds)) return -1;
     HIPCHK(c->order_out.grow(nout));
     a.out = c->order_out;
     hipLaunchKernelGGL(k_site_order_stats, dim3((unsigned)(count * a.nm.L)), dim3(EPX_QT_THREADS), lds, c->stream, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, a.out, nout * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
     if (nsamp) *nsamp = S;
-    return 0;
+    return sync.finish();
 }
 
 int epx_pooled_count_pass(epx_ctx *c, int k0, int count, const int32_t *names, int n_names, int shift,
@@ -1332,15 +1270,12 @@ int epx_pooled_count_pass(epx_ctx *c, int k0, int count, const int32_t *names, i
         }
     }
     CountArgs a;
-    if (named_call_args(c, "epx_pooled_count_pass", k0, count, names, n_names, theta, &S, a.nm)) return -1;
+    DrawSource src;
     // the row of the pool is sized by the sites of the RANGE (all alike), not by the context's largest site
-    a.nm.off[0] = 0;
-    for (int i = 0; i < n_names; ++i) a.nm.off[i + 1] = a.nm.off[i] + named_len(names[i], a.nm.model, a.nm.D, a.nm.d, a.nm.gauss, ng0);
-    for (int i = n_names; i < EPX_NM_MAX_REQ; ++i) a.nm.off[i + 1] = a.nm.off[n_names];
-    a.nm.L = a.nm.off[n_names];
+    if (named_front(c, "epx_pooled_count_pass", k0, count, names, n_names, theta, S, ng0, a.nm, &src)) return -1;
     const size_t L = (size_t)a.nm.L, nt = (size_t)n_targets;
     a.ng = ng0; a.shift = shift; a.n_targets = n_targets;
-    a.n = (long long)count * S;
+    a.n = (long long)count * src.S;
     a.tile = EPX_QT_MAX_TILE;
     while (a.tile > 1 && (count_lds_bytes(a.tile, n_targets) > EPX_QT_COUNT_LDS || (size_t)a.tile / 2 >= L)) a.tile /= 2;
     const size_t lds = count_lds_bytes(a.tile, n_targets);
@@ -1352,10 +1287,9 @@ int epx_pooled_count_pass(epx_ctx *c, int k0, int count, const int32_t *names, i
     if (nslab < (a.n + (1 << 20) - 1) / (1 << 20)) nslab = (a.n + (1 << 20) - 1) / (1 << 20);
     a.slab_rows = (a.n + nslab - 1) / nslab;
     nslab = (a.n + a.slab_rows - 1) / a.slab_rows;
-    if (nslab > 65535) {
-        (void)hipStreamSynchronize(c->stream);            // (a copy of injected draws may be queued: it ends before the caller has the array back)
-        return fail("epx_pooled_count_pass: %lld draws in one call, at most 65535 x 2^20", a.n);
-    }
+    if (nslab > 65535) return fail("epx_pooled_count_pass: %lld draws in one call, at most 65535 x 2^20", a.n);
+    StreamSync sync{c->stream};
+    if (upload_draws(c, src, &a.nm.draws)) return -1;
     const size_t n_hist = L * nt * 256;
     HIPCHK(c->count_ws.grow(n_hist + L + L * nt));
     a.hist = c->count_ws; a.n_nan = a.hist + n_hist;
@@ -1369,9 +1303,8 @@ int epx_pooled_count_pass(epx_ctx *c, int k0, int count, const int32_t *names, i
     static_assert(sizeof(long long) == sizeof(unsigned long long), "counts are copied as they are");
     HIPCHK(hipMemcpyAsync(hist, a.hist, n_hist * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(n_nan, a.n_nan, L * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
     *n = a.n;
-    return 0;
+    return sync.finish();
 }
 
 int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int32_t *row_group, const double *Xn,
@@ -1387,18 +1320,11 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
                         (long long)row_lim[j], (long long)row_lim[j + 1]);
     const int64_t n = row_lim[count];
     if (n > 0x7fffffff) return fail("epx_predict: %lld rows in one call, at most 2^31 - 1", (long long)n);
-    const size_t P = c->P, D = c->D;
+    const size_t D = c->D;
     PredictArgs a;
-    if (theta) {
-        if (S < 1) return fail("epx_predict: S = %d draws", S);
-    } else {
-        S = c->s_chains * c->s_nkeep;
-        if (!c->draws || S < 1 || c->drawn_count < 1) return fail("no draws yet");
-        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
-            return fail("epx_predict: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only",
-                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
-    }
-    if (nsamp) *nsamp = S;
+    DrawSource src;
+    if (draw_source(c, "epx_predict", k0, count, theta, S, nullptr, &src)) return -1;
+    if (nsamp) *nsamp = src.S;
     if (n == 0) return 0;
     if (!Xn || !out) return fail("epx_predict: Xn and out are required");
     if (yn && !c->gauss)
@@ -1426,15 +1352,7 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
         }
         for (int64_t i = lo; i < hi; ++i) perm[(size_t)lo + at[row_group ? row_group[i] : 0]++] = (int)i;
     }
-    if (theta) {
-        const size_t need = (size_t)count * S * P;
-        HIPCHK(c->inj.grow(need));
-        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
-        a.draws = c->inj;
-    } else {
-        a.draws = c->draws + (size_t)k0 * S * P;
-    }
-    a.model = c->model; a.D = c->D; a.d = c->d; a.gauss = c->gauss; a.P = c->P; a.S = S;
+    a.model = c->model; a.D = c->D; a.d = c->d; a.gauss = c->gauss; a.P = c->P; a.S = src.S;
     a.KP = (1 + c->D + 3) / 4 * 4;
     a.k0 = k0; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
     const size_t nn = (size_t)n, nwg = wg.size();
@@ -1443,25 +1361,18 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
     double *X_d = c->pred_ws, *y_d = X_d + nn * D, *out_d = y_d + nn;
     int *wg_d = c->pred_iws, *perm_d = wg_d + 4 * nwg;
     static_assert(sizeof(PredictWg) == 4 * sizeof(int), "PredictWg is four ints");
-    {
-        // `perm` and `wg` are this frame's: once their copies are queued nothing returns before the stream has been
-        // synchronised
-        hipError_t e = hipMemcpyAsync(X_d, Xn, nn * D * 8, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && yn) e = hipMemcpyAsync(y_d, yn, nn * 8, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(wg_d, wg.data(), nwg * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(perm_d, perm.data(), nn * sizeof(int), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            a.wg = reinterpret_cast<const PredictWg *>(wg_d); a.perm = perm_d;
-            a.X = X_d; a.y = yn ? y_d : nullptr; a.out = out_d;
-            hipLaunchKernelGGL(k_predict, dim3((unsigned)nwg), dim3(256), 0, c->stream, a);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, out_d, nn * EPX_PR_COUNT * 8, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t es = hipStreamSynchronize(c->stream);
-        HIPCHK(e);
-        HIPCHK(es);
-    }
-    return 0;
+    StreamSync sync{c->stream};          // (`perm` and `wg` are this frame's: the guard is declared behind them)
+    if (upload_draws(c, src, &a.draws)) return -1;
+    HIPCHK(hipMemcpyAsync(X_d, Xn, nn * D * 8, hipMemcpyHostToDevice, c->stream));
+    if (yn) HIPCHK(hipMemcpyAsync(y_d, yn, nn * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(wg_d, wg.data(), nwg * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(perm_d, perm.data(), nn * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    a.wg = reinterpret_cast<const PredictWg *>(wg_d); a.perm = perm_d;
+    a.X = X_d; a.y = yn ? y_d : nullptr; a.out = out_d;
+    hipLaunchKernelGGL(k_predict, dim3((unsigned)nwg), dim3(256), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, out_d, nn * EPX_PR_COUNT * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync.finish();
 }
 
 // LDS of the per-row PSIS stage (psis.h): 16 rows' scratch
@@ -1472,22 +1383,10 @@ int epx_loo(epx_ctx *c, int k0, int count, const double *theta, int S, double *o
     if (check_range(c, k0, count)) return -1;
     if (c->D > EPX_PR_DMAX) return fail("epx_loo: D = %d columns, at most %d", c->D, (int)EPX_PR_DMAX);
     if (!out) return fail("epx_loo: out is required");
-    const size_t P = c->P;
     LooArgs a;
-    if (theta) {
-        if (S < 1) return fail("epx_loo: S = %d draws", S);
-        const size_t need = (size_t)count * S * P;
-        HIPCHK(c->inj.grow(need));
-        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
-        a.p.draws = c->inj;
-    } else {
-        S = c->s_chains * c->s_nkeep;
-        if (!c->draws || S < 1 || c->drawn_count < 1) return fail("no draws yet");
-        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
-            return fail("epx_loo: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only",
-                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
-        a.p.draws = c->draws + (size_t)k0 * S * P;
-    }
+    DrawSource src;
+    if (draw_source(c, "epx_loo", k0, count, theta, S, nullptr, &src)) return -1;
+    S = src.S;
     if (nsamp) *nsamp = S;
     a.p.model = c->model; a.p.D = c->D; a.p.d = c->d; a.p.gauss = c->gauss; a.p.P = c->P; a.p.S = S;
     a.p.KP = (1 + c->D + 3) / 4 * 4;
@@ -1536,20 +1435,14 @@ int epx_loo(epx_ctx *c, int k0, int count, const double *theta, int S, double *o
     a.nwg = (int)nwg;
     int *wg_d = c->pred_iws;
     if (set_lds(k_loo, lds)) return -1;
-    {
-        // `wg` is this frame's: once its copy is queued nothing returns before the stream has been synchronised
-        hipError_t e = hipMemcpyAsync(wg_d, wg.data(), nwg * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            a.p.wg = reinterpret_cast<const PredictWg *>(wg_d);
-            hipLaunchKernelGGL(k_loo, dim3(grid), dim3(256), lds, c->stream, a);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, a.out, n_out * 8, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t es = hipStreamSynchronize(c->stream);
-        HIPCHK(e);
-        HIPCHK(es);
-    }
-    return 0;
+    StreamSync sync{c->stream};          // (`wg` is this frame's: the guard is declared behind it)
+    if (upload_draws(c, src, &a.p.draws)) return -1;
+    HIPCHK(hipMemcpyAsync(wg_d, wg.data(), nwg * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream));
+    a.p.wg = reinterpret_cast<const PredictWg *>(wg_d);
+    hipLaunchKernelGGL(k_loo, dim3(grid), dim3(256), lds, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, a.out, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync.finish();
 }
 
 int epx_draw_diagnostics(epx_ctx *c, int k0, int count, const double *theta, int S, int chains, double *out, int *nsamp) {
@@ -1558,24 +1451,9 @@ int epx_draw_diagnostics(epx_ctx *c, int k0, int count, const double *theta, int
     if (!out) return fail("epx_draw_diagnostics: out is required");
     const size_t P = c->P;
     DiagArgs a;
-    if (theta) {
-        if (S < 1) return fail("epx_draw_diagnostics: S = %d draws", S);
-        if (chains < 1 || chains > EPX_DG_MAX_CHAINS)
-            return fail("epx_draw_diagnostics: chains must be in 1..%d (got %d)", (int)EPX_DG_MAX_CHAINS, chains);
-        if (S % chains != 0) return fail("epx_draw_diagnostics: S = %d draws are no multiple of chains = %d", S, chains);
-        const size_t need = (size_t)count * S * P;
-        HIPCHK(c->inj.grow(need));
-        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
-        a.draws = c->inj;
-    } else {
-        chains = c->s_chains;
-        S = c->s_chains * c->s_nkeep;
-        if (!c->draws || S < 1 || c->drawn_count < 1) return fail("no draws yet");
-        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
-            return fail("epx_draw_diagnostics: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only",
-                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
-        a.draws = c->draws + (size_t)k0 * S * P;
-    }
+    DrawSource src;
+    if (draw_source(c, "epx_draw_diagnostics", k0, count, theta, S, &chains, &src)) return -1;
+    S = src.S; chains = src.chains;
     a.k0 = k0; a.chains = chains; a.nkeep = S / chains; a.P = c->P;
     a.d = c->d; a.pg = c->pg; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
     const int n = 2 * chains * (a.nkeep / 2);
@@ -1583,6 +1461,8 @@ int epx_draw_diagnostics(epx_ctx *c, int k0, int count, const double *theta, int
     a.in_lds = diag_lds_doubles(chains, a.nkeep, true) * 8 + 1024 <= LDS_CAP;
     const size_t lds = diag_lds_doubles(chains, a.nkeep, a.in_lds != 0) * 8;
     if (set_lds(k_draw_diag, lds)) return -1;
+    StreamSync sync{c->stream};
+    if (upload_draws(c, src, &a.draws)) return -1;
     const size_t nout = (size_t)count * P * EPX_DG_COUNT;
     HIPCHK(c->diag_out.grow(nout));
     a.out = c->diag_out;
@@ -1590,9 +1470,8 @@ int epx_draw_diagnostics(epx_ctx *c, int k0, int count, const double *theta, int
                        c->stream, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, a.out, nout * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
     if (nsamp) *nsamp = n;
-    return 0;
+    return sync.finish();
 }
 
 int epx_pooled_moments(epx_ctx *c, int k0, int count, const double *center, const double *theta, int S, int want_scatter,
@@ -1601,24 +1480,14 @@ int epx_pooled_moments(epx_ctx *c, int k0, int count, const double *center, cons
     if (check_range(c, k0, count)) return -1;
     if (!sum || !n) return fail("epx_pooled_moments: sum and n are required");
     if (want_scatter && !scatter) return fail("epx_pooled_moments: want_scatter without a scatter array");
-    const size_t P = c->P, d = c->d;
+    const size_t d = c->d;
     PooledArgs a;
-    if (theta) {
-        if (S < 1) return fail("epx_pooled_moments: S = %d draws", S);
-        const size_t need = (size_t)count * S * P;
-        HIPCHK(c->inj.grow(need));
-        HIPCHK(hipMemcpyAsync(c->inj, theta, need * 8, hipMemcpyHostToDevice, c->stream));
-        a.draws = c->inj;
-    } else {
-        S = c->s_chains * c->s_nkeep;
-        if (!c->draws || S < 1 || c->drawn_count < 1) return fail("no draws yet");
-        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
-            return fail("epx_pooled_moments: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only",
-                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
-        a.draws = c->draws + (size_t)k0 * S * P;
-    }
+    DrawSource src;
+    if (draw_source(c, "epx_pooled_moments", k0, count, theta, S, nullptr, &src)) return -1;
+    StreamSync sync{c->stream};
+    if (upload_draws(c, src, &a.draws)) return -1;
     a.d = c->d; a.P = c->P; a.nt = (c->d + 15) / 16; a.want_scatter = want_scatter ? 1 : 0;
-    a.n = (long long)count * S;
+    a.n = (long long)count * src.S;
     // the slabs depend on (n, d) alone: the same partition, hence the same bits, on every call.  About 2048 workgroups
     // (eight per compute unit) of at least 128 records each; whole groups of 16 records (four per wave and step)
     const int pairs = want_scatter ? a.nt * (a.nt + 1) / 2 : a.nt;
@@ -1640,9 +1509,8 @@ int epx_pooled_moments(epx_ctx *c, int k0, int count, const double *center, cons
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(sum, a.out_sum, d * 8, hipMemcpyDeviceToHost, c->stream));
     if (want_scatter) HIPCHK(hipMemcpyAsync(scatter, a.out_scatter, d * d * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
     *n = a.n;
-    return 0;
+    return sync.finish();
 }
 
 static int launch_global(epx_ctx *c, const double *packed_dev, double df, int want_moments,

@@ -1,5 +1,6 @@
 // Private to libepx.so: the context behind the opaque epx_ctx of include/epx.h, shared by
-// epx_api.hip (entry points) and epx_comm.hip (the in-library RCCL binding).
+// epx_api.hip (entry points), epx_draws.h (where an entry that post-processes draws finds them, and how it names
+// parameters) and epx_comm.hip (the in-library RCCL binding).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -103,7 +104,7 @@ struct epx_ctx {
     DevBuf<int64_t> seeds_d;
     DevBuf<double> dbg;             // [1+P] lp, grad ; [P] theta (test hook)
     DevBuf<int64_t> dbg_seed;
-    DevBuf<double> inj;             // injected samples (test hook)
+    DevBuf<double> inj;             // draws the caller passed in place of the sampler's (epx_draws.h: upload_draws; epx_moments_batch)
     DevBuf<double> named_out;       // epx_named_moments: [mean | M2] records of the call
     DevBuf<double> pooled_ws;       // epx_pooled_moments: [partial tiles | partial sums | scatter | sum | centre]
     DevBuf<double> pred_ws;         // epx_predict: [new rows (n x D) | responses (n) | results (n x EPX_PR_COUNT)]

@@ -1,0 +1,97 @@
+// Private to libepx.so (host only): what every entry point that post-processes draws has in front of its kernel --
+// epx_named_moments, epx_named_order_stats, epx_pooled_count_pass, epx_predict, epx_loo, epx_draw_diagnostics and
+// epx_pooled_moments.  The draws are those the last sampling call left in c->draws, or `theta` (count, S, P) of the caller,
+// copied to c->inj.
+// Order of refusals in an entry: its own arguments; for the named entries the name list, then every name in turn; the
+// draw source (draw_source: S, chains, "no draws yet", the sites drawn); whatever the entry derives from S; and only
+// then the first copy (upload_draws), behind a StreamSync -- from there on every exit has synchronised c->stream,
+// because the queued copies read the caller's memory.
+#pragma once
+#include "epx_ctx.h"
+#include "epx_kernels.h"
+
+namespace epx {
+
+struct DrawSource {
+    int S = 0, chains = 0;           // draws per site; chains they came from (an entry that passed `chains`)
+    const double *theta = nullptr;   // the caller's draws, or NULL: c->draws + at
+    size_t at = 0, need = 0;         // first double of site k0 in c->draws; doubles of theta
+};
+
+// Pure (no HIP call): refuses, or says how many draws per site the call has and where they are.  chains: NULL, or the
+// chains of injected draws (epx_draw_diagnostics); draws of the sampler come in c->s_chains chains.
+inline int draw_source(const epx_ctx *c, const char *who, int k0, int count, const double *theta, int S, const int *chains,
+                       DrawSource *src) {
+    src->theta = theta;
+    if (theta) {
+        if (S < 1) return fail("%s: S = %d draws", who, S);
+        if (chains) {
+            if (*chains < 1 || *chains > EPX_DG_MAX_CHAINS)
+                return fail("%s: chains must be in 1..%d (got %d)", who, (int)EPX_DG_MAX_CHAINS, *chains);
+            if (S % *chains != 0) return fail("%s: S = %d draws are no multiple of chains = %d", who, S, *chains);
+            src->chains = *chains;
+        }
+    } else {
+        S = c->s_chains * c->s_nkeep;
+        if (!c->draws || S < 1 || c->drawn_count < 1) return fail("no draws yet");
+        if (k0 < c->drawn_k0 || k0 + count > c->drawn_k0 + c->drawn_count)
+            return fail("%s: sites [%d,%d) asked, the last sampling call left draws of sites [%d,%d) only", who,
+                        k0, k0 + count, c->drawn_k0, c->drawn_k0 + c->drawn_count);
+        src->chains = c->s_chains;
+    }
+    src->S = S;
+    src->at = (size_t)k0 * S * c->P;
+    src->need = (size_t)count * S * c->P;
+    return 0;
+}
+
+// The device pointer of a source: injected draws are queued for copy into c->inj (grown), on c->stream.
+inline int upload_draws(epx_ctx *c, const DrawSource &src, const double **draws) {
+    if (src.theta) {
+        HIPCHK(c->inj.grow(src.need));
+        HIPCHK(hipMemcpyAsync(c->inj, src.theta, src.need * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    *draws = src.theta ? c->inj : c->draws + src.at;
+    return 0;
+}
+
+// Declared in front of the first queued copy that reads caller memory: whichever way the entry is left, the stream has
+// been synchronised.  The good path ends with `return sync.finish();`, which reports the synchronisation's own error.
+struct StreamSync {
+    hipStream_t stream;
+    bool pending = true;
+    ~StreamSync() { if (pending) (void)hipStreamSynchronize(stream); }
+    int finish() {
+        pending = false;
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+};
+
+// name, off and L of `a` for sites of ng groups: off[i] = first element of name i's block in a row of L elements
+// (the slots behind n_names repeat L); model, D, d and gauss come from the context.
+inline int named_layout(const epx_ctx *c, const int32_t *names, int n_names, int ng, NamedArgs &a) {
+    a.n_names = n_names; a.off[0] = 0;
+    for (int i = 0; i < EPX_NM_MAX_REQ; ++i) {
+        const int n = i < n_names ? named_len(names[i], c->model, c->D, c->d, c->gauss, ng) : 0;
+        if (n < 0) return fail("named parameter %d is not defined by this site model", (int)names[i]);
+        a.name[i] = i < n_names ? names[i] : 0; a.off[i + 1] = a.off[i] + n;
+    }
+    a.L = a.off[n_names];
+    return 0;
+}
+
+// Everything of the NamedArgs of a call over named parameters but `draws`, rows laid out for ng groups; pure.
+inline int named_front(const epx_ctx *c, const char *who, int k0, int count, const int32_t *names, int n_names,
+                       const double *theta, int S, int ng, NamedArgs &a, DrawSource *src) {
+    if (!names || n_names < 1 || n_names > EPX_NM_MAX_REQ) return fail("%s: between 1 and %d names", who, (int)EPX_NM_MAX_REQ);
+    a.model = c->model; a.D = c->D; a.d = c->d; a.gauss = c->gauss; a.P = c->P;
+    a.ng_max = c->ng_max; a.k0 = k0; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    a.draws = nullptr; a.mean = a.m2 = nullptr;
+    if (named_layout(c, names, n_names, ng, a)) return -1;
+    if (draw_source(c, who, k0, count, theta, S, nullptr, src)) return -1;
+    a.S = src->S;
+    return 0;
+}
+
+}  // namespace epx

@@ -474,45 +474,16 @@ class HipEngine(object):
         centred sum of squares in the per-site shapes of site_params.named_draws.  The draws are those of the last
         sampling call, on the device; `theta` (count, S, P) injects draws instead (test hook)."""
         count = self.K - k0 if count is None else count
-        names = [names] if isinstance(names, str) else list(names)
-        for name in names:
-            if name not in _site_params.NAME_IDS:
-                raise ValueError('unknown parameter name {!r} (known: {})'.format(name, sorted(_site_params.NAME_IDS)))
-        ids = np.array([_site_params.NAME_IDS[name] for name in names], dtype=np.int32)
-        mid, gauss, sg = MODEL_IDS[self.model] % 5, is_gauss(self.model), self.model.endswith('_sg')
-        ng_max = 1 if self.g_cnt is None else int(self.g_cnt.max())
-        S = 0
-        if theta is not None:
-            theta = np.ascontiguousarray(theta, dtype=np.float64)
-            if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
-                raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
-            S = theta.shape[1]
-        # the widest site's lengths size a row; an undefined name fails in the library like any other error
-        lens = []
-        for i in ids:
-            n = ctypes.c_int()
-            check(self.lib.epx_named_len(self.ctx, int(np.argmax(self.g_cnt)) if self.g_cnt is not None else 0, int(i),
-                                         ctypes.byref(n)))
-            lens.append(n.value)
+        names, ids = self._named_ids(names)
+        theta, S = self._injected(theta, count)
+        lens = self._named_lens(ids, self._widest_site())
         L = int(sum(lens))
         mean = np.zeros((count, L))
         m2 = np.zeros((count, L))
         n = ctypes.c_int()
         check(self.lib.epx_named_moments(self.ctx, int(k0), int(count), ids.ctypes.data_as(_lib.c_int32_p), len(names),
                                          dptr(theta), int(S), dptr(mean), dptr(m2), ctypes.byref(n)))
-        off = np.concatenate(([0], np.cumsum(lens)))
-        means, m2s = [], []
-        for b in range(count):
-            ng = 1 if self.g_cnt is None else int(self.g_cnt[k0 + b])
-            dm, dv = {}, {}
-            for j, name in enumerate(names):
-                shape = _site_params.named_shape(mid, self.D, ng, gauss, sg, name)
-                size = int(np.prod(shape, dtype=np.int64))
-                dm[name] = mean[b, off[j]:off[j] + size].reshape(shape).copy()
-                dv[name] = m2[b, off[j]:off[j] + size].reshape(shape).copy()
-            means.append(dm)
-            m2s.append(dv)
-        return n.value, means, m2s
+        return n.value, self._cut_sites(names, lens, mean, k0), self._cut_sites(names, lens, m2, k0)
 
     def predict(self, Xn, row_lim, row_group=None, y=None, k0=0, count=None, theta=None):
         """Posterior predictive of new rows (epx_predict, include/epx.h): (n, 4), columns site_params.PR_MEAN,
@@ -535,12 +506,7 @@ class HipEngine(object):
             y = np.ascontiguousarray(y, dtype=np.float64)
             if y.shape != (Xn.shape[0],):
                 raise ValueError('y: one response per new row')
-        S = 0
-        if theta is not None:
-            theta = np.ascontiguousarray(theta, dtype=np.float64)
-            if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
-                raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
-            S = theta.shape[1]
+        theta, S = self._injected(theta, count)
         out = np.zeros((Xn.shape[0], _site_params.PR_COUNT))
         check(self.lib.epx_predict(self.ctx, int(k0), int(count), row_lim.ctypes.data_as(_lib.c_int64_p),
                                    row_group.ctypes.data_as(_lib.c_int32_p) if row_group is not None else None,
@@ -553,12 +519,7 @@ class HipEngine(object):
         draws are those of the last sampling call, on the device; `theta` (count, S, P) injects draws instead (test
         hook).  with_n: also return the draws per site."""
         count = self.K - k0 if count is None else count
-        S = 0
-        if theta is not None:
-            theta = np.ascontiguousarray(theta, dtype=np.float64)
-            if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
-                raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
-            S = theta.shape[1]
+        theta, S = self._injected(theta, count)
         ok = 0 <= k0 and count >= 1 and k0 + count <= self.K        # (a bad range: the library says so)
         rows = int(self.k_lim[k0 + count] - self.k_lim[k0]) if ok else 0
         out = np.zeros((rows, _loo.LO_COUNT))
@@ -582,14 +543,9 @@ class HipEngine(object):
         call, on the device; `theta` (count, S, P), chain-major, with `chains` injects draws instead (test hook).
         with_n: also return the used draws per site."""
         count = self.K - k0 if count is None else count
-        S = 0
-        if theta is not None:
-            if chains is None:
-                raise ValueError('injected draws need `chains`')
-            theta = np.ascontiguousarray(theta, dtype=np.float64)
-            if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
-                raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
-            S = theta.shape[1]
+        if theta is not None and chains is None:
+            raise ValueError('injected draws need `chains`')
+        theta, S = self._injected(theta, count)
         out = np.zeros((max(int(count), 0), self.P, _diagnostics.DG_COUNT))
         n = ctypes.c_int()
         check(self.lib.epx_draw_diagnostics(self.ctx, int(k0), int(count), dptr(theta), int(S),
@@ -603,12 +559,7 @@ class HipEngine(object):
         `theta` (count, S, P) injects draws instead (test hook)."""
         count = self.K - k0 if count is None else count
         d = self.d
-        S = 0
-        if theta is not None:
-            theta = np.ascontiguousarray(theta, dtype=np.float64)
-            if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
-                raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
-            S = theta.shape[1]
+        theta, S = self._injected(theta, count)
         if center is not None:
             center = np.ascontiguousarray(center, dtype=np.float64)
             if center.shape != (d,):
@@ -636,7 +587,29 @@ class HipEngine(object):
             lens.append(n.value)
         return lens
 
+    def _widest_site(self):
+        """The site whose lengths size a row of the per-site calls over named parameters."""
+        return int(np.argmax(self.g_cnt)) if self.g_cnt is not None else 0
+
+    def _cut_sites(self, names, lens, rows, k0, lead=()):
+        """rows (count,) + lead + (L,), every site's names side by side at the widest site's lengths `lens` -> a list, one
+        entry per site, of {name: lead + the per-site shape of site_params.named_draws}."""
+        mid, gauss, sg = MODEL_IDS[self.model] % 5, is_gauss(self.model), self.model.endswith('_sg')
+        off = np.concatenate(([0], np.cumsum(lens)))
+        sites, cuts = [], {}                             # cuts: per group count, (name, first, last, shape) of every name
+        for b in range(rows.shape[0]):
+            ng = 1 if self.g_cnt is None else int(self.g_cnt[k0 + b])
+            if ng not in cuts:
+                shapes = [_site_params.named_shape(mid, self.D, ng, gauss, sg, name) for name in names]
+                cuts[ng] = [(name, o, o + int(np.prod(sh, dtype=np.int64)), lead + sh)
+                            for name, o, sh in zip(names, off, shapes)]
+            row = rows[b]
+            sites.append(dict((name, np.array(row[..., lo:hi], order='C').reshape(shape))      # (np.array: its own copy)
+                              for name, lo, hi, shape in cuts[ng]))
+        return sites
+
     def _injected(self, theta, count):
+        """`theta` (count, S, P) as the library takes it, and S; (None, 0): the draws of the last sampling call."""
         if theta is None:
             return None, 0
         theta = np.ascontiguousarray(theta, dtype=np.float64)
@@ -653,24 +626,13 @@ class HipEngine(object):
         count = self.K - k0 if count is None else count
         names, ids = self._named_ids(names)
         ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
-        mid, gauss, sg = MODEL_IDS[self.model] % 5, is_gauss(self.model), self.model.endswith('_sg')
         theta, S = self._injected(theta, count)
-        lens = self._named_lens(ids, int(np.argmax(self.g_cnt)) if self.g_cnt is not None else 0)
+        lens = self._named_lens(ids, self._widest_site())
         L, R = int(sum(lens)), int(ranks.size)
         out = np.zeros((max(int(count), 0), L, R))
         check(self.lib.epx_named_order_stats(self.ctx, int(k0), int(count), ids.ctypes.data_as(_lib.c_int32_p), len(names),
                                              ranks.ctypes.data_as(_lib.c_int64_p), R, dptr(theta), int(S), dptr(out), None))
-        off = np.concatenate(([0], np.cumsum(lens)))
-        stats = []
-        for b in range(count):
-            ng = 1 if self.g_cnt is None else int(self.g_cnt[k0 + b])
-            rec = {}
-            for j, name in enumerate(names):
-                shape = _site_params.named_shape(mid, self.D, ng, gauss, sg, name)
-                size = int(np.prod(shape, dtype=np.int64))
-                rec[name] = np.ascontiguousarray(out[b, off[j]:off[j] + size].T).reshape((R,) + shape)
-            stats.append(rec)
-        return stats
+        return self._cut_sites(names, lens, out.swapaxes(1, 2), k0, (R,))
 
     def pooled_count_pass(self, names, shift, prefix, n_targets, k0=0, count=None, theta=None):
         """One counting pass of the pooled selection over the draws of the sites k0..k0+count (epx_pooled_count_pass,

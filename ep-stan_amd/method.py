@@ -659,6 +659,15 @@ class Master(object):
         out_m[...] = m
         return out_S, out_m
 
+    def _need_draws(self, what, refusal):
+        """Refuses what reads the draws of the last iteration on the device while there are none: `what` can not be done
+        before an iteration; injected draws hold phi only, `refusal`."""
+        if self.iter == 0:
+            raise RuntimeError("Can not {} before at least one iteration has been done.".format(what))
+        if self._draws_injected:
+            raise RuntimeError("The draws of the last iteration were injected (`_sample_injector`): they hold phi "
+                               "only, {}.".format(refusal))
+
     def _site_spec(self):
         """(b-model id, Gaussian family, single-group program) of the site model, as site_params takes them."""
         name = self.model_name
@@ -681,33 +690,43 @@ class Master(object):
             m2s.append(v)
         return n, means, m2s
 
-    def _gather_named(self, names, n, means, m2s):
-        """Per-site records of ALL sites on every rank: ns (K), and lists of {name: ndarray}.  One record per site,
-        [n | means | M2s] flattened and padded to the widest site, gathered like the site arrays."""
-        K = self.K
-        if self.comm.world == 1:
-            return np.full(K, n, dtype=np.int64), means, m2s
+    def _gather_site_records(self, names, local, R, head=None):
+        """Records of named parameters of ALL sites on every rank from this rank's: `local` holds one {name: (R,) + the
+        per-site shape} per local site, the result one per site.  One record per site -- its R rows of the site's
+        elements side by side, flattened, padded to the widest site -- is gathered like the site arrays.  head: a number
+        of this rank that travels in front of each of its records; then (sites, heads (K)) is returned."""
+        K, h = self.K, 0 if head is None else 1
         mid, gauss, sg = self._site_spec()
         shapes = [[_site_params.named_shape(mid, self.D, int(self._site_ng[k]), gauss, sg, name) for name in names]
                   for k in range(K)]
         sizes = [[int(np.prod(sh, dtype=np.int64)) for sh in row] for row in shapes]
         W = max(sum(row) for row in sizes)
-        rec = np.zeros((2 * W + 1, self.K_local), order='F')
-        rec[0, :] = n
+        rec = np.zeros((h + R * W, self.K_local), order='F')
+        if h:
+            rec[0, :] = head
         for j in range(self.K_local):
-            rec[1:1 + sum(sizes[self.k_lo + j]), j] = np.concatenate([np.ravel(means[j][name]) for name in names])
-            rec[1 + W:1 + W + sum(sizes[self.k_lo + j]), j] = np.concatenate([np.ravel(m2s[j][name]) for name in names])
+            flat = np.concatenate([local[j][name].reshape(R, -1) for name in names], axis=1)      # (R, the site's elements)
+            rec[h:, j].reshape(R, W)[:, :flat.shape[1]] = flat
         full = self.comm.allgather_sites(rec, K)
-        ms, vs = [], []
+        sites = []
         for k in range(K):
-            dm, dv, at = {}, {}, 0
+            rows, d, at = np.ascontiguousarray(full[h:, k]).reshape(R, W), {}, 0
             for name, sh, size in zip(names, shapes[k], sizes[k]):
-                dm[name] = full[1 + at:1 + at + size, k].reshape(sh)
-                dv[name] = full[1 + W + at:1 + W + at + size, k].reshape(sh)
+                d[name] = rows[:, at:at + size].reshape((R,) + tuple(sh))
                 at += size
-            ms.append(dm)
-            vs.append(dv)
-        return np.rint(full[0, :]).astype(np.int64), ms, vs
+            sites.append(d)
+        return (sites, full[0, :]) if h else sites
+
+    def _gather_named(self, names, n, means, m2s):
+        """Per-site records of ALL sites on every rank: ns (K), and lists of {name: ndarray}.  The record of a site is
+        [n | means | M2s]: two rows behind the draws per site."""
+        if self.comm.world == 1:
+            return np.full(self.K, n, dtype=np.int64), means, m2s
+        local = [dict((name, np.stack([np.asarray(m[name]), np.asarray(v[name])])) for name in names)
+                 for m, v in zip(means, m2s)]
+        both, ns = self._gather_site_records(names, local, 2, head=n)
+        return (np.rint(ns).astype(np.int64), [dict((name, d[name][0]) for name in names) for d in both],
+                [dict((name, d[name][1]) for name in names) for d in both])
 
     def mix_pred(self, params, smap=None, param_shapes=None):
         """Mean and variance of named parameters of the site model from the tilted draws of the last iteration
@@ -721,11 +740,7 @@ class Master(object):
         the kernel k_named_moments reduces them to per-site (mean, centred sum of squares) records, and only those
         are combined on the host (mix_pred.combine_moments) -- no `save_last_param` needed.  With several ranks the
         records are gathered over the communicator; every rank returns the same result."""
-        if self.iter == 0:
-            raise RuntimeError("Can not mix samples before at least one iteration has been done.")
-        if self._draws_injected:
-            raise RuntimeError("The draws of the last iteration were injected (`_sample_injector`): they hold phi "
-                               "only, named parameters can not be mixed.")
+        self._need_draws("mix samples", "named parameters can not be mixed")
         only_one_param = isinstance(params, str)
         if only_one_param:
             params, smap, param_shapes = [params], [smap], [param_shapes]
@@ -774,32 +789,13 @@ class Master(object):
         """Per-site order statistics of ALL sites on every rank: a list of {name: (len(ranks),) + per-site shape}.  Every
         rank selects its own sites' (HipEngine.named_order_stats, or quantiles.site_order_stats_host on an engine
         without it); one record per site, flattened and padded to the widest site, is gathered like the site arrays."""
-        eng, R, K = self.engine, len(ranks), self.K
-        mid, gauss, sg = self._site_spec()
+        eng = self.engine
         if hasattr(eng, 'named_order_stats'):
             local = eng.named_order_stats(names, ranks)
         else:
             local = [dict((name, _quantiles.order_stats(d[name], ranks)) for name in names)
                      for d in (self._local_named_draws(names, j) for j in range(self.K_local))]
-        if self.comm.world == 1:
-            return local
-        shapes = [[_site_params.named_shape(mid, self.D, int(self._site_ng[k]), gauss, sg, name) for name in names]
-                  for k in range(K)]
-        sizes = [[int(np.prod(sh, dtype=np.int64)) for sh in row] for row in shapes]
-        W = max(sum(row) for row in sizes)
-        rec = np.zeros((R * W, self.K_local), order='F')
-        for j in range(self.K_local):
-            flat = np.concatenate([local[j][name].reshape(R, -1) for name in names], axis=1)      # (R, the site's elements)
-            rec[:, j].reshape(R, W)[:, :flat.shape[1]] = flat
-        full = self.comm.allgather_sites(rec, K)
-        stats = []
-        for k in range(K):
-            row, d, at = np.ascontiguousarray(full[:, k]).reshape(R, W), {}, 0
-            for name, sh, size in zip(names, shapes[k], sizes[k]):
-                d[name] = row[:, at:at + size].reshape((R,) + tuple(sh))
-                at += size
-            stats.append(d)
-        return stats
+        return local if self.comm.world == 1 else self._gather_site_records(names, local, len(ranks))
 
     def mix_quantiles(self, params, probs=(0.025, 0.25, 0.5, 0.75, 0.975), smap=None, param_shapes=None):
         """Quantiles of named parameters of the site model from the tilted draws of the last iteration: the credible
@@ -820,11 +816,7 @@ class Master(object):
         Only order statistics leave the device; the host interpolates (quantiles.interpolate).  An engine without the
         device methods (the CPU oracle the tests inject) goes through the host functions of quantiles.py.  With several
         ranks every rank returns the same result."""
-        if self.iter == 0:
-            raise RuntimeError("Can not mix samples before at least one iteration has been done.")
-        if self._draws_injected:
-            raise RuntimeError("The draws of the last iteration were injected (`_sample_injector`): they hold phi "
-                               "only, named parameters can not be mixed.")
+        self._need_draws("mix samples", "named parameters can not be mixed")
         only_one_param = isinstance(params, str)
         if only_one_param:
             params, smap, param_shapes = [params], [smap], [param_shapes]
@@ -916,11 +908,7 @@ class Master(object):
         rows in the caller's order.  The draws stay in device memory, the kernel k_predict reduces them to four
         numbers per row.  With several ranks every rank computes the rows of its own sites and one all-reduce makes
         every rank return the same result."""
-        if self.iter == 0:
-            raise RuntimeError("Can not predict before at least one iteration has been done.")
-        if self._draws_injected:
-            raise RuntimeError("The draws of the last iteration were injected (`_sample_injector`): they hold phi "
-                               "only, nothing can be predicted from them.")
+        self._need_draws("predict", "nothing can be predicted from them")
         if (site_sizes is None) == (site_ind is None):
             raise ValueError("Give exactly one of `site_sizes` and `site_ind`")
         X_new = np.asarray(X_new, dtype=np.float64)
@@ -1030,11 +1018,7 @@ class Master(object):
         The draws stay in device memory: the kernel k_loo forms every row's log-likelihoods under its site's draws
         on the matrix pipe, keeps them on chip and reduces them to six numbers per row.  With several ranks every
         rank computes the rows of its own sites and one all-reduce makes every rank return the same result."""
-        if self.iter == 0:
-            raise RuntimeError("Can not cross-validate before at least one iteration has been done.")
-        if self._draws_injected:
-            raise RuntimeError("The draws of the last iteration were injected (`_sample_injector`): they hold phi "
-                               "only, nothing can be cross-validated from them.")
+        self._need_draws("cross-validate", "nothing can be cross-validated from them")
         lo, hi = int(self.k_lim[self.k_lo]), int(self.k_lim[self.k_hi])
         loc, S = self._local_loo()
         rec = loc
@@ -1067,11 +1051,7 @@ class Master(object):
         without `draw_diagnostics` (the CPU oracle the tests inject) hands its draws to `diagnostics.diagnostics_host`.
         With several ranks every rank computes its own sites and the records are gathered over the communicator:
         every rank returns the same result."""
-        if self.iter == 0:
-            raise RuntimeError("Can not diagnose draws before at least one iteration has been done.")
-        if self._draws_injected:
-            raise RuntimeError("The draws of the last iteration were injected (`_sample_injector`): they hold phi "
-                               "only, nothing can be diagnosed from them.")
+        self._need_draws("diagnose draws", "nothing can be diagnosed from them")
         eng, C = self.engine, _diagnostics.DG_COUNT
         chains = int(self.workers[self.k_lo].stan_params['chains'])
         ng_local = self._site_ng[self.k_lo:self.k_hi]
