@@ -19,6 +19,7 @@
 #include "psis.h"
 #include "epx_ctx.h"
 #include "epx_draws.h"
+#include "epx_update.h"
 
 using namespace epx;
 
@@ -80,31 +81,51 @@ int epx_model_dims(int model, int D, int *dphi, int *npar) {
     return 0;
 }
 
-// room behind the packed site sums for the statistics that ride on the same all-reduce
-// (epx_update_trial: 8 sums + 8 maxima x up to 120 ranks) and the three trial flags
-enum { STAT_CAP = 8, PACKED_EXTRA = 1024 };
 int epx_comm_allreduce_dev(epx_ctx *c, double *buf, size_t n, int op);      // epx_comm.hip
-
-static inline int ld_of(int d) { return d | 1; }
-static inline size_t dense_slot_doubles(int d) { return 2 * (size_t)d * ld_of(d) + 4 * (size_t)ld_of(d); }
-
-// LDS or global workspace (grown in `buf`) for `nblocks` concurrent dense blocks
-static int dense_ws(DevBuf<double> &buf, int d, int nblocks, DenseWs *ws, size_t *lds_bytes) {
-    const size_t bytes = dense_slot_doubles(d) * 8;
-    if (bytes + 1024 <= LDS_CAP) { ws->use_lds = 1; ws->global = nullptr; *lds_bytes = bytes; return 0; }
-    ws->use_lds = 0; *lds_bytes = 0;
-    HIPCHK(buf.grow(dense_slot_doubles(d) * nblocks));
-    ws->global = buf;
-    return 0;
-}
 
 template <typename K>
 static int set_lds(K kern, size_t bytes) {
     if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) return fail("hipFuncSetAttribute(%zu): %s", bytes, hipGetErrorString(e));
     }
+    return 0;
+}
+
+// Queues one dense kernel (dense.hip) at dimension d: `grid` blocks of 256 threads, their work matrices in dynamic LDS or
+// in `buf`, grown to `nblocks` slots (epx_update.h: DensePlan).  d, ld and ws of the argument struct are filled here.
+template <typename Args>
+static int launch_dense(void (*kern)(Args), int grid, hipStream_t stream, DevBuf<double> &buf, int d, int nblocks, Args &a) {
+    const DensePlan p(d);
+    HIPCHK(buf.grow(p.ws_doubles(nblocks)));            // (no doubles, no allocation, while the matrices are in LDS)
+    a.d = d; a.ld = p.ld;
+    a.ws.use_lds = p.in_lds; a.ws.global = p.in_lds ? nullptr : buf.p;
+    if (set_lds(kern, p.lds_bytes)) return -1;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), p.lds_bytes, stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// A caller's array that may only be read goes up to the device; one that may be written is filled from it.
+static hipError_t copy_host(double *dev, const double *host, size_t n) { return hipMemcpy(dev, host, n * 8, hipMemcpyHostToDevice); }
+static hipError_t copy_host(double *dev, double *host, size_t n) { return hipMemcpy(host, dev, n * 8, hipMemcpyDeviceToHost); }
+
+// The accessors' pair of synchronous copies between the caller's arrays Qh, rh (H: const double or double, as above) and records
+// [k, k + count) of two device arrays (d x d and d doubles a record): each only if the caller gave its array.
+template <typename H>
+static int copy_pair(const epx_ctx *c, double *Qd, double *rd, size_t k, size_t count, H *Qh, H *rh) {
+    const size_t d = c->d;
+    if (Qh) HIPCHK(copy_host(Qd + k * d * d, Qh, count * d * d));
+    if (rh) HIPCHK(copy_host(rd + k * d, rh, count * d));
+    return 0;
+}
+
+// Queued: (Qo, ro) = (Qi, ri) + df (dQi, dri) over all sites -- the proposal of a trial, or in place the accepted update
+static int queue_site_axpy(epx_ctx *c, double *Qo, double *ro, double df) {
+    const size_t K = c->K, d = c->d;
+    hipLaunchKernelGGL(k_axpy, dim3(1024), dim3(256), 0, c->stream, Qo, c->Qi, c->dQi, df, K * d * d);
+    hipLaunchKernelGGL(k_axpy, dim3(64), dim3(256), 0, c->stream, ro, c->ri, c->dri, df, K * d);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -283,9 +304,7 @@ int epx_ctx_destroy(epx_ctx *c) {
 
 int epx_set_prior(epx_ctx *c, const double *Q0, const double *r0) {
     CTX(c);
-    HIPCHK(hipMemcpy(c->Q0, Q0, (size_t)c->d * c->d * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->r0, r0, (size_t)c->d * 8, hipMemcpyHostToDevice));
-    return 0;
+    return copy_pair(c, c->Q0, c->r0, 0, 1, Q0, r0);
 }
 
 static int check_range(epx_ctx *c, int k0, int count) {
@@ -302,120 +321,96 @@ static int site_ptrs(epx_ctx *c, int which, double **Q, double **r) {
     return fail("unknown site array %d", which);
 }
 
-int epx_set_sites(epx_ctx *c, int which, const double *QF, const double *rF) {
-    CTX(c);
+// sites [k, k + count) of a site array to or from the caller's arrays (copy_pair)
+template <typename H>
+static int copy_sites(epx_ctx *c, int which, int k, int count, H *Qh, H *rh) {
     double *Q, *r;
     if (site_ptrs(c, which, &Q, &r)) return -1;
-    const size_t K = c->K, d = c->d;
-    if (QF) HIPCHK(hipMemcpy(Q, QF, K * d * d * 8, hipMemcpyHostToDevice));
-    if (rF) HIPCHK(hipMemcpy(r, rF, K * d * 8, hipMemcpyHostToDevice));
-    return 0;
+    return copy_pair(c, Q, r, k, count, Qh, rh);
+}
+
+int epx_set_sites(epx_ctx *c, int which, const double *QF, const double *rF) {
+    CTX(c);
+    return copy_sites(c, which, 0, c->K, QF, rF);
 }
 
 int epx_get_sites(epx_ctx *c, int which, double *QF, double *rF) {
     CTX(c);
-    double *Q, *r;
-    if (site_ptrs(c, which, &Q, &r)) return -1;
-    const size_t K = c->K, d = c->d;
     if (which == EPX_QI2) {
         // materialise the proposal Qi + df*dQi of the last trial (method.py:1071-1072)
-        hipLaunchKernelGGL(k_axpy, dim3(1024), dim3(256), 0, c->stream, c->Qi2, c->Qi, c->dQi, c->last_df, K * d * d);
-        hipLaunchKernelGGL(k_axpy, dim3(64), dim3(256), 0, c->stream, c->ri2, c->ri, c->dri, c->last_df, K * d);
+        if (queue_site_axpy(c, c->Qi2, c->ri2, c->last_df)) return -1;
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    if (QF) HIPCHK(hipMemcpy(QF, Q, K * d * d * 8, hipMemcpyDeviceToHost));
-    if (rF) HIPCHK(hipMemcpy(rF, r, K * d * 8, hipMemcpyDeviceToHost));
-    return 0;
+    return copy_sites(c, which, 0, c->K, QF, rF);
 }
 
 int epx_set_site(epx_ctx *c, int which, int k, const double *Qh, const double *rh) {
     CTX(c);
     if (check_range(c, k, 1)) return -1;
-    double *Q, *r;
-    if (site_ptrs(c, which, &Q, &r)) return -1;
-    const size_t d = c->d;
-    if (Qh) HIPCHK(hipMemcpy(Q + (size_t)k * d * d, Qh, d * d * 8, hipMemcpyHostToDevice));
-    if (rh) HIPCHK(hipMemcpy(r + (size_t)k * d, rh, d * 8, hipMemcpyHostToDevice));
-    return 0;
+    return copy_sites(c, which, k, 1, Qh, rh);
 }
 
 int epx_get_site(epx_ctx *c, int which, int k, double *Qh, double *rh) {
     CTX(c);
     if (check_range(c, k, 1)) return -1;
-    double *Q, *r;
-    if (site_ptrs(c, which, &Q, &r)) return -1;
     if (which == EPX_QI2) return fail("epx_get_site: use epx_get_sites for the proposal array");
-    const size_t d = c->d;
-    if (Qh) HIPCHK(hipMemcpy(Qh, Q + (size_t)k * d * d, d * d * 8, hipMemcpyDeviceToHost));
-    if (rh) HIPCHK(hipMemcpy(rh, r + (size_t)k * d, d * 8, hipMemcpyDeviceToHost));
-    return 0;
+    return copy_sites(c, which, k, 1, Qh, rh);
 }
 
 int epx_set_global(epx_ctx *c, const double *Q, const double *r) {
     CTX(c);
-    if (Q) HIPCHK(hipMemcpy(c->Q, Q, (size_t)c->d * c->d * 8, hipMemcpyHostToDevice));
-    if (r) HIPCHK(hipMemcpy(c->r, r, (size_t)c->d * 8, hipMemcpyHostToDevice));
-    return 0;
+    return copy_pair(c, c->Q, c->r, 0, 1, Q, r);
 }
 int epx_get_global(epx_ctx *c, double *Q, double *r) {
     CTX(c);
-    if (Q) HIPCHK(hipMemcpy(Q, c->Q, (size_t)c->d * c->d * 8, hipMemcpyDeviceToHost));
-    if (r) HIPCHK(hipMemcpy(r, c->r, (size_t)c->d * 8, hipMemcpyDeviceToHost));
-    return 0;
+    return copy_pair(c, c->Q, c->r, 0, 1, Q, r);
 }
 
 static int launch_cavity(epx_ctx *c, const double *Qs, const double *rs, const double *dQs,
                          const double *drs, double df, int k0, int count) {
     CavityArgs a;
-    a.k0 = k0; a.d = c->d; a.ld = ld_of(c->d);
-    size_t lds;
-    if (dense_ws(c->dense_ws, c->d, count, &a.ws, &lds)) return -1;
+    a.k0 = k0;
     a.Q = c->Q; a.r = c->r; a.Qsite = Qs; a.rsite = rs; a.dQsite = dQs; a.drsite = drs;
     a.site_stride = (size_t)c->d * c->d; a.rsite_stride = c->d; a.df = df;
     a.cav_Om = c->cav_Om; a.cav_mu = c->cav_mu; a.flags = c->flags;
-    if (set_lds(k_cavity, lds)) return -1;
-    hipLaunchKernelGGL(k_cavity, dim3(count), dim3(256), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
+    return launch_dense(k_cavity, count, c->stream, c->dense_ws, c->d, count, a);
+}
+
+// Queued: the cavities of the proposals Qi + df dQi, ri + df dri of sites [k0, k0 + count) against the global approximation
+static int launch_proposal_cavities(epx_ctx *c, double df, int k0, int count) { return launch_cavity(c, c->Qi, c->ri, c->dQi, c->dri, df, k0, count); }
+
+// The tail of the entries that leave per-site flags: the stream synchronised, then those of sites [k0, k0 + count) to the caller
+static int fetch_flags(epx_ctx *c, int k0, int count, uint8_t *out) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (out) HIPCHK(hipMemcpy(out, c->flags + k0, count, hipMemcpyDeviceToHost));
     return 0;
 }
 
 int epx_cavity_batch(epx_ctx *c, int which, int k0, int count, uint8_t *posdef) {
     CTX(c);
     if (check_range(c, k0, count)) return -1;
-    int rc;
-    if (which == EPX_QI) rc = launch_cavity(c, c->Qi, c->ri, nullptr, nullptr, 0.0, k0, count);
-    else if (which == EPX_QI2) rc = launch_cavity(c, c->Qi, c->ri, c->dQi, c->dri, c->last_df, k0, count);
-    else return fail("cavity needs EPX_QI or EPX_QI2");
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (posdef) HIPCHK(hipMemcpy(posdef, c->flags + k0, count, hipMemcpyDeviceToHost));
-    return 0;
+    if (which != EPX_QI && which != EPX_QI2) return fail("cavity needs EPX_QI or EPX_QI2");
+    if (which == EPX_QI ? launch_cavity(c, c->Qi, c->ri, nullptr, nullptr, 0.0, k0, count)
+                        : launch_proposal_cavities(c, c->last_df, k0, count)) return -1;
+    return fetch_flags(c, k0, count, posdef);
 }
 
 int epx_cavity_site(epx_ctx *c, int k, const double *Q, const double *r, const double *Qi,
                     const double *ri, uint8_t *posdef) {
     CTX(c);
     if (check_range(c, k, 1)) return -1;
-    const size_t d = c->d;
     // the caller's arrays become the context's state for this site (Worker.cavity
     // aliases Q, r: method.py:286-287)
-    HIPCHK(hipMemcpy(c->Q, Q, d * d * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->r, r, d * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->Qi2 + (size_t)k * d * d, Qi, d * d * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->ri2 + (size_t)k * d, ri, d * 8, hipMemcpyHostToDevice));
+    if (copy_pair(c, c->Q, c->r, 0, 1, Q, r)) return -1;
+    if (copy_pair(c, c->Qi2, c->ri2, k, 1, Qi, ri)) return -1;
     if (launch_cavity(c, c->Qi2, c->ri2, nullptr, nullptr, 0.0, k, 1)) return -1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (posdef) HIPCHK(hipMemcpy(posdef, c->flags + k, 1, hipMemcpyDeviceToHost));
-    return 0;
+    return fetch_flags(c, k, 1, posdef);
 }
 
 int epx_get_cavity(epx_ctx *c, int k, double *Mat, double *vec) {
     CTX(c);
     if (check_range(c, k, 1)) return -1;
-    const size_t d = c->d;
-    if (Mat) HIPCHK(hipMemcpy(Mat, c->cav_Om + (size_t)k * d * d, d * d * 8, hipMemcpyDeviceToHost));
-    if (vec) HIPCHK(hipMemcpy(vec, c->cav_mu + (size_t)k * d, d * 8, hipMemcpyDeviceToHost));
-    return 0;
+    return copy_pair(c, c->cav_Om, c->cav_mu, k, 1, Mat, vec);
 }
 
 // ------------------------------------------------------------------ sampler
@@ -868,21 +863,21 @@ static int run_sampler(epx_ctx *c, int k0, int count, const int64_t *seeds, cons
     return 0;
 }
 
-static int launch_moments(epx_ctx *c, int k0, int count, const double *draws, long site0,
-                          long stride_site, long stride_s, long stride_i, int S, int prec_estim) {
+// what the moment stage refuses of a call's draws, in front of any copy of them
+static int check_moments(const epx_ctx *c, int S, int prec_estim) {
     if (prec_estim != EPX_PREC_SAMPLE && prec_estim != EPX_PREC_OLSE) return fail("bad prec_estim %d", prec_estim);
     if (S < c->d) return fail("fewer draws (%d) than dimensions (%d)", S, c->d);   // method.py:427 raises ValueError
+    return 0;
+}
+
+static int launch_moments(epx_ctx *c, int k0, int count, const double *draws, long site0,
+                          long stride_site, long stride_s, long stride_i, int S, int prec_estim) {
     MomentArgs a;
-    a.k0 = k0; a.d = c->d; a.ld = ld_of(c->d); a.S = S; a.prec_estim = prec_estim;
-    size_t lds;
-    if (dense_ws(c->dense_ws, c->d, count, &a.ws, &lds)) return -1;
+    a.k0 = k0; a.S = S; a.prec_estim = prec_estim;
     a.draws = draws; a.draws_site0 = site0; a.stride_site = stride_site; a.stride_s = stride_s; a.stride_i = stride_i;
     a.Q = c->Q; a.r = c->r; a.dQi = c->dQi; a.dri = c->dri;
     a.tilt_mean = c->tilt_mean; a.tilt_scatter = c->tilt_scatter; a.flags = c->flags;
-    if (set_lds(k_moments, lds)) return -1;
-    hipLaunchKernelGGL(k_moments, dim3(count), dim3(256), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_dense(k_moments, count, c->stream, c->dense_ws, c->d, count, a);
 }
 
 int epx_sample_batch(epx_ctx *c, int k0, int count, const int64_t *seeds, const epx_sampler_opts *opts,
@@ -916,11 +911,11 @@ int epx_tilted_batch(epx_ctx *c, int k0, int count, const int64_t *seeds, const 
     if (norm_opts(opts, &o)) return -1;
     if (run_sampler(c, k0, count, seeds, o, elapsed_ms)) return -1;
     const int nkeep = c->s_nkeep;
+    if (check_moments(c, o.chains * nkeep, prec_estim)) return -1;
     // native draw layout: (site, chain, keep, P) -> draw s = chain*nkeep + keep is contiguous
     if (launch_moments(c, k0, count, c->draws, k0, (long)o.chains * nkeep * c->P, c->P, 1,
                        o.chains * nkeep, prec_estim)) return -1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (posdef) HIPCHK(hipMemcpy(posdef, c->flags + k0, count, hipMemcpyDeviceToHost));
+    if (fetch_flags(c, k0, count, posdef)) return -1;
     if (stats) HIPCHK(hipMemcpy(stats, c->site_stats, (size_t)count * 8 * 8, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -929,23 +924,21 @@ int epx_moments_batch(epx_ctx *c, int k0, int count, const double *samples, int 
                       uint8_t *posdef) {
     CTX(c);
     if (check_range(c, k0, count)) return -1;
+    if (check_moments(c, S, prec_estim)) return -1;
     const size_t need = (size_t)count * S * c->d;
     HIPCHK(c->inj.grow(need));
     HIPCHK(hipMemcpy(c->inj, samples, need * 8, hipMemcpyHostToDevice));
     // (S, d) F-order per site: element (s, i) at i*S + s
     if (launch_moments(c, k0, count, c->inj, 0, (long)S * c->d, 1, S, S, prec_estim)) return -1;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (fetch_flags(c, k0, count, posdef)) return -1;
     c->nsamp = S;
-    if (posdef) HIPCHK(hipMemcpy(posdef, c->flags + k0, count, hipMemcpyDeviceToHost));
     return 0;
 }
 
 int epx_get_tilted(epx_ctx *c, int k, double *Mat, double *vec, int *nsamp) {
     CTX(c);
     if (check_range(c, k, 1)) return -1;
-    const size_t d = c->d;
-    if (Mat) HIPCHK(hipMemcpy(Mat, c->tilt_scatter + (size_t)k * d * d, d * d * 8, hipMemcpyDeviceToHost));
-    if (vec) HIPCHK(hipMemcpy(vec, c->tilt_mean + (size_t)k * d, d * 8, hipMemcpyDeviceToHost));
+    if (copy_pair(c, c->tilt_scatter, c->tilt_mean, k, 1, Mat, vec)) return -1;
     if (nsamp) *nsamp = c->nsamp;
     return 0;
 }
@@ -1147,34 +1140,37 @@ int epx_packed_len(epx_ctx *c, int *len) {
     return 0;
 }
 
-int epx_site_sums(epx_ctx *c, double *packed_host, double *packed_dev) {
-    CTX(c);
+// Queued: `len` sums over the sites' arrays Qi, ri, dQi, dri into `out`: `partial` per slice of sites (c->partial), k_site_sums_final across them
+static int queue_site_sums(epx_ctx *c, void (*partial)(SumArgs), int len, const double *Qi, const double *ri,
+                           const double *dQi, const double *dri, double *out) {
     SumArgs a;
-    a.K = c->K; a.d = c->d; a.len = 2 * (c->d * c->d + c->d); a.nslice = c->nslice;
-    a.Qi = c->Qi; a.ri = c->ri; a.dQi = c->dQi; a.dri = c->dri;
-    a.partial = c->partial; a.out = packed_dev ? packed_dev : c->packed;
-    const int nb = (a.len + 255) / 256;
-    hipLaunchKernelGGL(k_site_sums_partial, dim3(nb, a.nslice), dim3(256), 0, c->stream, a);
+    a.K = c->K; a.d = c->d; a.len = len; a.nslice = c->nslice;
+    a.Qi = Qi; a.ri = ri; a.dQi = dQi; a.dri = dri;
+    a.partial = c->partial; a.out = out;
+    const int nb = (len + 255) / 256;
+    hipLaunchKernelGGL(partial, dim3(nb, a.nslice), dim3(256), 0, c->stream, a);
     hipLaunchKernelGGL(k_site_sums_final, dim3(nb), dim3(256), 0, c->stream, a);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int epx_site_sums(epx_ctx *c, double *packed_host, double *packed_dev) {
+    CTX(c);
+    const int len = 2 * (c->d * c->d + c->d);
+    double *out = packed_dev ? packed_dev : c->packed;
+    if (queue_site_sums(c, k_site_sums_partial, len, c->Qi, c->ri, c->dQi, c->dri, out)) return -1;
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (packed_host) HIPCHK(hipMemcpy(packed_host, a.out, (size_t)a.len * 8, hipMemcpyDeviceToHost));
+    if (packed_host) HIPCHK(hipMemcpy(packed_host, out, (size_t)len * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
 int epx_mix_sums(epx_ctx *c, double *out) {
     CTX(c);
     if (!c->nsamp) return fail("no tilted moments yet");
-    SumArgs a;
-    a.K = c->K; a.d = c->d; a.len = 2 * c->d * c->d + c->d; a.nslice = c->nslice;
-    a.Qi = c->tilt_scatter; a.ri = c->tilt_mean; a.dQi = nullptr; a.dri = nullptr;
-    a.partial = c->partial; a.out = c->packed;
-    const int nb = (a.len + 255) / 256;
-    hipLaunchKernelGGL(k_mix_partial, dim3(nb, a.nslice), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(k_site_sums_final, dim3(nb), dim3(256), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    const int len = 2 * c->d * c->d + c->d;
+    if (queue_site_sums(c, k_mix_partial, len, c->tilt_scatter, c->tilt_mean, nullptr, nullptr, c->packed)) return -1;
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(out, a.out, (size_t)a.len * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, c->packed, (size_t)len * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1517,41 +1513,50 @@ static int launch_global(epx_ctx *c, const double *packed_dev, double df, int wa
                          const double *tgt = nullptr, double *crit = nullptr) {
     GlobalArgs a;
     a.tgt = tgt; a.crit = crit;
-    a.d = c->d; a.ld = ld_of(c->d); a.want_moments = want_moments;
-    size_t lds;
-    if (dense_ws(c->dense_ws, c->d, c->K, &a.ws, &lds)) return -1;
+    a.want_moments = want_moments;
     a.packed = packed_dev; a.Q0 = c->Q0; a.r0 = c->r0; a.df = df;
     a.Q = c->Q; a.r = c->r; a.S = c->S; a.m = c->m; a.flag = c->iflags;
-    if (set_lds(k_global, lds)) return -1;
-    hipLaunchKernelGGL(k_global, dim3(1), dim3(256), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
+    // (one block, but the workspace is sized for the cavities that follow: it does not grow between the two)
+    return launch_dense(k_global, 1, c->stream, c->dense_ws, c->d, c->K, a);
+}
+
+// Queued: one damping trial -- the global approximation from the packed sums at `df`, then every site's cavity against it.
+// (epx_damped_trial queues the two halves itself: it looks at the global check in between.)
+static int launch_trial(epx_ctx *c, const double *packed_dev, double df, int want_moments,
+                        const double *tgt = nullptr, double *crit = nullptr) {
+    if (launch_global(c, packed_dev, df, want_moments, tgt, crit)) return -1;
+    return launch_proposal_cavities(c, df, 0, c->K);
+}
+
+// The packed sums a trial reads: the caller's host array, queued for copy into c->packed (behind the caller's
+// StreamSync); else the caller's device array; else c->packed, the sums of the last epx_site_sums on this rank.
+static int trial_sums(epx_ctx *c, const double *packed_host, const double *packed_dev, const double **pk) {
+    *pk = packed_host || !packed_dev ? c->packed : packed_dev;
+    if (packed_host) HIPCHK(hipMemcpyAsync(c->packed, packed_host, (size_t)2 * (c->d * c->d + c->d) * 8, hipMemcpyHostToDevice, c->stream));
     return 0;
 }
 
 int epx_damped_trial(epx_ctx *c, double df, const double *packed_host, const double *packed_dev,
                      int *global_pd, int *cav_pd, int *first_bad) {
     CTX(c);
-    const double *pk = packed_dev;
-    if (packed_host) {
-        HIPCHK(hipMemcpyAsync(c->packed, packed_host, (size_t)2 * (c->d * c->d + c->d) * 8,
-                              hipMemcpyHostToDevice, c->stream));
-        pk = c->packed;
-    }
-    if (!pk) pk = c->packed;       // sums of the last epx_site_sums on this rank
+    int h[4] = {0, 0, -1, 0};
+    const double *pk;
+    StreamSync global_sync{c->stream};
+    if (trial_sums(c, packed_host, packed_dev, &pk)) return -1;
     c->last_df = df;
     if (launch_global(c, pk, df, 0)) return -1;
-    int h[4] = {0, 0, -1, 0};
     HIPCHK(hipMemcpyAsync(h, c->iflags, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (global_sync.finish()) return -1;
     *global_pd = h[0];
     *cav_pd = 0;
     if (first_bad) *first_bad = -1;
-    if (!h[0]) return 0;
-    if (launch_cavity(c, c->Qi, c->ri, c->dQi, c->dri, df, 0, c->K)) return -1;
+    if (!h[0]) return 0;           // the documented early exit: cavities run only behind a positive definite global check
+    StreamSync sync{c->stream};
+    if (launch_proposal_cavities(c, df, 0, c->K)) return -1;
     hipLaunchKernelGGL(k_all_flags, dim3(1), dim3(256), 0, c->stream, c->flags, 0, c->K, c->iflags + 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h + 1, c->iflags + 1, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (sync.finish()) return -1;
     *cav_pd = h[1];
     if (first_bad) *first_bad = h[2];
     return 0;
@@ -1561,60 +1566,37 @@ int epx_update_trial(epx_ctx *c, double df, int reduce_sums, int site_base, doub
                      double *stat_max, int n_max, int want_moments, int *global_pd, int *cav_pd,
                      int64_t *first_bad, double *S, double *m) {
     CTX(c);
-    if (n_sum < 0 || n_sum > STAT_CAP || n_max < 0 || n_max > STAT_CAP) return fail("at most %d statistics of a kind", STAT_CAP);
     const bool bound = c->comm || c->comm_ext;
-    const int nr = bound ? c->comm_size : 1, rank = bound ? c->comm_rank : 0;
+    TrialStats st;
+    if (trial_stats(n_sum, n_max, bound ? c->comm_size : 1, bound ? c->comm_rank : 0, &st)) return -1;
     const int len = 2 * (c->d * c->d + c->d);
-    const int next = n_sum + n_max * nr;
-    if (next + 3 > PACKED_EXTRA) return fail("too many ranks (%d) for the statistics block", nr);
-    double *ext_d = c->packed + len, *trial_d = c->packed + len + PACKED_EXTRA - 3;
-    std::vector<double> ext((size_t)next + 1, 0.0);
+    const size_t next = st.count();
+    double *ext_d = c->packed + len, *trial_d = ext_d + TRIAL_FLAGS_AT;
+    // (the host ends of the queued copies stand in front of the guard: they outlive its synchronisation on every exit)
+    std::vector<double> ext(next + 1, 0.0);
+    double tf[3] = {0, 0, 0};
+    StreamSync sync{c->stream};
     if (reduce_sums) {
-        // statistics of this rank: sums as they are, maxima in the rank's own slots (the others stay 0,
-        // so the sum over ranks is an all-gather and the maximum is taken on the host)
-        for (int i = 0; i < n_sum; ++i) ext[i] = stat_sum[i];
-        for (int i = 0; i < n_max; ++i) ext[n_sum + (size_t)rank * n_max + i] = stat_max[i];
-        if (next) HIPCHK(hipMemcpyAsync(ext_d, ext.data(), (size_t)next * 8, hipMemcpyHostToDevice, c->stream));
-        SumArgs a;
-        a.K = c->K; a.d = c->d; a.len = len; a.nslice = c->nslice;
-        a.Qi = c->Qi; a.ri = c->ri; a.dQi = c->dQi; a.dri = c->dri;
-        a.partial = c->partial; a.out = c->packed;
-        const int nb = (a.len + 255) / 256;
-        hipLaunchKernelGGL(k_site_sums_partial, dim3(nb, a.nslice), dim3(256), 0, c->stream, a);
-        hipLaunchKernelGGL(k_site_sums_final, dim3(nb), dim3(256), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        st.pack(stat_sum, stat_max, ext.data());
+        if (next) HIPCHK(hipMemcpyAsync(ext_d, ext.data(), next * 8, hipMemcpyHostToDevice, c->stream));
+        if (queue_site_sums(c, k_site_sums_partial, len, c->Qi, c->ri, c->dQi, c->dri, c->packed)) return -1;
         // the ONE reduction of the iteration (method.py:1073-1074; affine in df, so it serves every trial)
-        if (epx_comm_allreduce_dev(c, c->packed, (size_t)len + next, EPX_OP_SUM)) return -1;
+        if (epx_comm_allreduce_dev(c, c->packed, len + next, EPX_OP_SUM)) return -1;
     }
     c->last_df = df;
-    if (launch_global(c, c->packed, df, want_moments)) return -1;
-    if (launch_cavity(c, c->Qi, c->ri, c->dQi, c->dri, df, 0, c->K)) return -1;
+    if (launch_trial(c, c->packed, df, want_moments)) return -1;
     hipLaunchKernelGGL(k_trial_flags, dim3(1), dim3(256), 0, c->stream, c->flags, c->K, site_base, c->iflags, trial_d);
     HIPCHK(hipGetLastError());
     if (epx_comm_allreduce_dev(c, trial_d, 3, EPX_OP_MIN)) return -1;
-    double tf[3] = {0, 0, 0};
-    {
-        // Once a device-to-host copy into this frame's buffers is queued, nothing returns before the stream has been
-        // synchronised: a copy that lands after an early return would write into a dead stack frame
-        hipError_t e = hipMemcpyAsync(tf, trial_d, sizeof tf, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && reduce_sums && next) e = hipMemcpyAsync(ext.data(), ext_d, (size_t)next * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && want_moments && S) e = hipMemcpyAsync(S, c->S, (size_t)c->d * c->d * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && want_moments && m) e = hipMemcpyAsync(m, c->m, (size_t)c->d * 8, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t es = hipStreamSynchronize(c->stream);           // the one synchronisation of the trial
-        HIPCHK(e);
-        HIPCHK(es);
-    }
+    HIPCHK(hipMemcpyAsync(tf, trial_d, sizeof tf, hipMemcpyDeviceToHost, c->stream));
+    if (reduce_sums && next) HIPCHK(hipMemcpyAsync(ext.data(), ext_d, next * 8, hipMemcpyDeviceToHost, c->stream));
+    if (want_moments && S) HIPCHK(hipMemcpyAsync(S, c->S, (size_t)c->d * c->d * 8, hipMemcpyDeviceToHost, c->stream));
+    if (want_moments && m) HIPCHK(hipMemcpyAsync(m, c->m, (size_t)c->d * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sync.finish()) return -1;                   // the one synchronisation of the trial
     *global_pd = tf[0] != 0.0;
     *cav_pd = tf[1] != 0.0;
-    if (first_bad) *first_bad = tf[2] >= 1e17 ? -1 : (int64_t)tf[2];
-    if (reduce_sums) {
-        for (int i = 0; i < n_sum; ++i) stat_sum[i] = ext[i];
-        for (int i = 0; i < n_max; ++i) {
-            double v = ext[n_sum + i];
-            for (int r = 1; r < nr; ++r) v = std::fmax(v, ext[n_sum + (size_t)r * n_max + i]);
-            stat_max[i] = v;
-        }
-    }
+    if (first_bad) *first_bad = TrialStats::first_bad(tf[2]);
+    if (reduce_sums) st.unpack(ext.data(), stat_sum, stat_max);
     return 0;
 }
 
@@ -1624,8 +1606,7 @@ int epx_damp_sweep(epx_ctx *c, int ndf, const double *dfs, const double *packed_
     CTX(c);
     if (ndf < 1 || !dfs || !m_target || !S_target || !out) return fail("damp sweep: missing argument");
     const size_t d = c->d, d2 = d * d, ntgt = 2 * (d + d2) + 2;
-    const size_t need = ntgt + (size_t)ndf * 5;
-    HIPCHK(c->sweep_buf.grow(need));
+    HIPCHK(c->sweep_buf.grow(ntgt + (size_t)ndf * 5));
     std::vector<double> h(ntgt, 0.0);
     memcpy(h.data(), m_target, d * 8);
     memcpy(h.data() + d, S_target, d2 * 8);
@@ -1633,65 +1614,48 @@ int epx_damp_sweep(epx_ctx *c, int ndf, const double *dfs, const double *packed_
     if (have_samp) { memcpy(h.data() + d + d2, samp_mean, d * 8); memcpy(h.data() + 2 * d + d2, samp_scatter, d2 * 8); }
     h[2 * (d + d2)] = half_logdet_S_target;
     h[2 * (d + d2) + 1] = have_samp ? (double)n_samp : 0.0;
+    StreamSync sync{c->stream};
     HIPCHK(hipMemcpyAsync(c->sweep_buf, h.data(), ntgt * 8, hipMemcpyHostToDevice, c->stream));
-    const double *pk = packed_dev;
-    if (packed_host) {
-        HIPCHK(hipMemcpyAsync(c->packed, packed_host, (size_t)2 * (d2 + d) * 8, hipMemcpyHostToDevice, c->stream));
-        pk = c->packed;
-    }
-    if (!pk) pk = c->packed;
+    const double *pk;
+    if (trial_sums(c, packed_host, packed_dev, &pk)) return -1;
     double *crit = c->sweep_buf + ntgt;
     // every trial back to back on the stream, one synchronisation at the end
     for (int i = 0; i < ndf; ++i) {
-        if (launch_global(c, pk, dfs[i], 1, c->sweep_buf, crit + (size_t)i * 5)) return -1;
-        if (launch_cavity(c, c->Qi, c->ri, c->dQi, c->dri, dfs[i], 0, c->K)) return -1;
+        if (launch_trial(c, pk, dfs[i], 1, c->sweep_buf, crit + (size_t)i * 5)) return -1;
         hipLaunchKernelGGL(k_all_flags, dim3(1), dim3(256), 0, c->stream, c->flags, 0, c->K, c->iflags + 1);
         hipLaunchKernelGGL(k_sweep_flag, dim3(1), dim3(64), 0, c->stream, c->iflags + 1, crit + (size_t)i * 5);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(out, crit, (size_t)ndf * 5 * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->last_df = dfs[ndf - 1];
-    return 0;
+    c->last_df = dfs[ndf - 1];       // (in front of the synchronisation: the good path ends with it; the orders differ only if it fails)
+    return sync.finish();
 }
 
 int epx_accept(epx_ctx *c, double df) {
     CTX(c);
-    const size_t K = c->K, d = c->d;
-    hipLaunchKernelGGL(k_axpy, dim3(1024), dim3(256), 0, c->stream, c->Qi, c->Qi, c->dQi, df, K * d * d);
-    hipLaunchKernelGGL(k_axpy, dim3(64), dim3(256), 0, c->stream, c->ri, c->ri, c->dri, df, K * d);
-    HIPCHK(hipGetLastError());
     // no synchronisation: every later use is ordered behind it on the context's stream (the
     // synchronous copies of the accessors run on the legacy default stream, which waits for it)
-    return 0;
+    return queue_site_axpy(c, c->Qi, c->ri, df);
 }
 
 int epx_global_moments(epx_ctx *c, double *S, double *m) {
     CTX(c);
-    if (launch_global(c, nullptr, 0.0, 1)) return -1;
     int ok = 0;
+    StreamSync sync{c->stream};
+    if (launch_global(c, nullptr, 0.0, 1)) return -1;
     HIPCHK(hipMemcpyAsync(&ok, c->iflags, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (sync.finish()) return -1;
     if (!ok) return fail("global precision is not positive definite");
-    if (S) HIPCHK(hipMemcpy(S, c->S, (size_t)c->d * c->d * 8, hipMemcpyDeviceToHost));
-    if (m) HIPCHK(hipMemcpy(m, c->m, (size_t)c->d * 8, hipMemcpyDeviceToHost));
-    return 0;
+    return copy_pair(c, c->S, c->m, 0, 1, S, m);
 }
 
 int epx_force_pd(epx_ctx *c, double df, double thresh, double min_eig_target, uint8_t *forced) {
     CTX(c);
     ForceArgs a;
-    a.d = c->d; a.ld = ld_of(c->d);
-    size_t lds;
-    if (dense_ws(c->dense_ws, c->d, c->K, &a.ws, &lds)) return -1;
     a.Qi = c->Qi; a.dQi = c->dQi; a.df = df; a.thresh = thresh; a.target = min_eig_target;
     a.forced = c->flags; a.min_eig = c->min_eig;
-    if (set_lds(k_force_pd, lds)) return -1;
-    hipLaunchKernelGGL(k_force_pd, dim3(c->K), dim3(256), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (forced) HIPCHK(hipMemcpy(forced, c->flags, c->K, hipMemcpyDeviceToHost));
-    return 0;
+    if (launch_dense(k_force_pd, c->K, c->stream, c->dense_ws, c->d, c->K, a)) return -1;
+    return fetch_flags(c, 0, c->K, forced);
 }
 
 // ------------------------------------------------------ stand-alone util ops
@@ -1717,19 +1681,15 @@ int epx_invert_normal_params(int device, int d, int nb, double *A, double *b, in
     if (need_device(device)) return -1;
     if (d < 1 || nb < 1) return fail("bad sizes");
     InvertArgs a;
-    a.d = d; a.ld = ld_of(d); a.cho_form = cho_form;
-    size_t lds;
+    a.cho_form = cho_form;
     DevBuf<double> ws, Ad, bd;
     DevBuf<int32_t> infod;
-    if (dense_ws(ws, d, nb, &a.ws, &lds)) return -1;
     HIPCHK(Ad.alloc((size_t)nb * d * d));
     HIPCHK(infod.alloc(nb));
     HIPCHK(hipMemcpy(Ad, A, (size_t)nb * d * d * 8, hipMemcpyHostToDevice));
     if (b) { HIPCHK(bd.alloc((size_t)nb * d)); HIPCHK(hipMemcpy(bd, b, (size_t)nb * d * 8, hipMemcpyHostToDevice)); }
     a.A = Ad; a.b = bd; a.info = infod;
-    if (set_lds(k_invert, lds)) return -1;
-    hipLaunchKernelGGL(k_invert, dim3(nb), dim3(256), lds, 0, a);
-    HIPCHK(hipGetLastError());
+    if (launch_dense(k_invert, nb, 0, ws, d, nb, a)) return -1;
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(A, Ad, (size_t)nb * d * d * 8, hipMemcpyDeviceToHost));
     if (b) HIPCHK(hipMemcpy(b, bd, (size_t)nb * d * 8, hipMemcpyDeviceToHost));
@@ -1742,19 +1702,15 @@ int epx_olse(int device, int d, int nb, double *S, int n, const double *P, int32
     if (need_device(device)) return -1;
     if (d < 1 || nb < 1) return fail("bad sizes");
     OlseArgs a;
-    a.d = d; a.ld = ld_of(d); a.n = n;
-    size_t lds;
+    a.n = n;
     DevBuf<double> ws, Sd, Pd;
     DevBuf<int32_t> infod;
-    if (dense_ws(ws, d, nb, &a.ws, &lds)) return -1;
     HIPCHK(Sd.alloc((size_t)nb * d * d));
     HIPCHK(infod.alloc(nb));
     HIPCHK(hipMemcpy(Sd, S, (size_t)nb * d * d * 8, hipMemcpyHostToDevice));
     if (P) { HIPCHK(Pd.alloc((size_t)nb * d * d)); HIPCHK(hipMemcpy(Pd, P, (size_t)nb * d * d * 8, hipMemcpyHostToDevice)); }
     a.S = Sd; a.P = Pd; a.info = infod;
-    if (set_lds(k_olse, lds)) return -1;
-    hipLaunchKernelGGL(k_olse, dim3(nb), dim3(256), lds, 0, a);
-    HIPCHK(hipGetLastError());
+    if (launch_dense(k_olse, nb, 0, ws, d, nb, a)) return -1;
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(S, Sd, (size_t)nb * d * d * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(info, infod, nb * sizeof(int32_t), hipMemcpyDeviceToHost));

@@ -1,6 +1,6 @@
 // Private to libepx.so: the context behind the opaque epx_ctx of include/epx.h, shared by
 // epx_api.hip (entry points), epx_draws.h (where an entry that post-processes draws finds them, and how it names
-// parameters) and epx_comm.hip (the in-library RCCL binding).
+// parameters), epx_update.h (what the update stage decides on the host) and epx_comm.hip (the in-library RCCL binding).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,6 +63,19 @@ struct DevBuf {
         release();
         p = q; n = want;
         return true;
+    }
+};
+
+// Declared in front of the first queued copy that reads or writes caller or stack memory, behind the host buffers of such
+// copies: whichever way the entry is left, the stream has been synchronised.  The good path ends with sync.finish().
+struct StreamSync {
+    hipStream_t stream;
+    bool pending = true;
+    ~StreamSync() { if (pending) (void)hipStreamSynchronize(stream); }
+    int finish() {
+        pending = false;
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
     }
 };
 

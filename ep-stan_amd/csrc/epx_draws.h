@@ -4,7 +4,7 @@
 // copied to c->inj.
 // Order of refusals in an entry: its own arguments; for the named entries the name list, then every name in turn; the
 // draw source (draw_source: S, chains, "no draws yet", the sites drawn); whatever the entry derives from S; and only
-// then the first copy (upload_draws), behind a StreamSync -- from there on every exit has synchronised c->stream,
+// then the first copy (upload_draws), behind a StreamSync (epx_ctx.h) -- from there on every exit has synchronised c->stream,
 // because the queued copies read the caller's memory.
 #pragma once
 #include "epx_ctx.h"
@@ -54,19 +54,6 @@ inline int upload_draws(epx_ctx *c, const DrawSource &src, const double **draws)
     *draws = src.theta ? c->inj : c->draws + src.at;
     return 0;
 }
-
-// Declared in front of the first queued copy that reads caller memory: whichever way the entry is left, the stream has
-// been synchronised.  The good path ends with `return sync.finish();`, which reports the synchronisation's own error.
-struct StreamSync {
-    hipStream_t stream;
-    bool pending = true;
-    ~StreamSync() { if (pending) (void)hipStreamSynchronize(stream); }
-    int finish() {
-        pending = false;
-        HIPCHK(hipStreamSynchronize(stream));
-        return 0;
-    }
-};
 
 // name, off and L of `a` for sites of ng groups: off[i] = first element of name i's block in a row of L elements
 // (the slots behind n_names repeat L); model, D, d and gauss come from the context.
