@@ -63,6 +63,9 @@ SIGNATURES = {
                                         c_double_p, c_double_p]),
     'epx_moments_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p,
                                          ctypes.c_int, ctypes.c_int, c_uint8_p]),
+    'epx_set_draw_reuse': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'epx_reweight_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
+                                          ctypes.c_int, c_double_p, c_double_p, c_uint8_p, c_double_p, c_double_p]),
     'epx_get_tilted': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_int_p]),
     'epx_get_draws': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p]),
     'epx_num_draws': (ctypes.c_int, [ctypes.c_void_p, c_int_p]),

@@ -8,6 +8,7 @@
 // 86-106), which are fused into the kernels below.
 #include "epx_device.h"
 #include "epx_kernels.h"
+#include "psis.h"
 
 namespace epx {
 
@@ -159,86 +160,88 @@ k_cavity(CavityArgs a) {
 // (lane l: k l>>4, col l&15); D: col = l&15, row = (l>>4) + 4*reg.
 typedef double v4d __attribute__((ext_vector_type(4)));
 
-// Worker.tilted moment stage (method.py:410-475) for one site per block.
-__global__ void __launch_bounds__(256)
-k_moments(MomentArgs a) {
-    extern __shared__ __align__(16) double lds[];
-    __shared__ double red[16];
-    __shared__ double scal[8];
-    const int k = a.k0 + blockIdx.x;
-    const int d = a.d, ld = a.ld, tid = threadIdx.x, T = blockDim.x, S = a.S;
-    double *W, *V, *vec;
-    ws_pointers(a.ws, blockIdx.x, d, ld, lds, W, V, vec);
-    double *mean = vec;            // d
-    const double *X = a.draws + (size_t)(a.draws_site0 + blockIdx.x) * a.stride_site;
-    const long ss = a.stride_s, si = a.stride_i;
-
-    // ---- mean over the S draws (method.py:415) : thread = (coordinate, slice)
-    {
-        int nsl = T / d;                          // slices of the draw index
-        if (nsl > d) nsl = d;
-        if (nsl < 1) nsl = 1;
-        for (int idx = tid; idx < d * nsl; idx += T) {       // d may exceed the block size
-            const int i = idx % d, sl = idx / d;
-            double s = 0.0;
-            for (int t = sl; t < S; t += nsl) s += X[(long)t * ss + (long)i * si];
-            V[i + (size_t)sl * ld] = s;          // slices are combined in a fixed order below
-        }
-        __syncthreads();
-        for (int i = tid; i < d; i += T) {
-            double s = 0.0;
-            for (int sl = 0; sl < nsl; ++sl) s += V[i + (size_t)sl * ld];
-            mean[i] = s / (double)S;
-        }
-        __syncthreads();
+// mean[i] = (1/S) sum_s X(s, i) (method.py:415): thread = (coordinate, slice of the draw index); V: d x ld of scratch
+__device__ inline void draw_mean(const double *X, long ss, long si, int S, int d, int ld, double *V, double *mean) {
+    const int tid = threadIdx.x, T = blockDim.x;
+    int nsl = T / d;                          // slices of the draw index
+    if (nsl > d) nsl = d;
+    if (nsl < 1) nsl = 1;
+    for (int idx = tid; idx < d * nsl; idx += T) {       // d may exceed the block size
+        const int i = idx % d, sl = idx / d;
+        double s = 0.0;
+        for (int t = sl; t < S; t += nsl) s += X[(long)t * ss + (long)i * si];
+        V[i + (size_t)sl * ld] = s;          // slices are combined in a fixed order below
     }
-    // ---- scatter C'C of the centred draws (method.py:417-420 / :444-446), MFMA f64
-    {
-        const int wave = tid >> 6, lane = tid & 63, nw = T >> 6;
-        const int nt = (d + 15) / 16;
-        const int ntile = nt * (nt + 1) / 2;
-        for (int tile = wave; tile < ntile; tile += nw) {
-            // unrank (ti <= tj)
-            int ti = 0, rem = tile;
-            while (rem >= nt - ti) { rem -= nt - ti; ++ti; }
-            const int tj = ti + rem;
-            const int ia = ti * 16 + (lane & 15), ib = tj * 16 + (lane & 15);
-            const double ma = ia < d ? mean[ia] : 0.0, mb = ib < d ? mean[ib] : 0.0;
-            const int kq = lane >> 4;
-            v4d acc = {0.0, 0.0, 0.0, 0.0};
-            for (int s0 = 0; s0 < S; s0 += 4) {
-                const int s = s0 + kq;
-                double av = 0.0, bv = 0.0;
-                if (s < S) {
-                    if (ia < d) av = X[(long)s * ss + (long)ia * si] - ma;
-                    if (ib < d) bv = X[(long)s * ss + (long)ib * si] - mb;
-                }
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = ti * 16 + (lane >> 4) + 4 * r, col = tj * 16 + (lane & 15);
-                if (row < d && col < d) {
-                    W[row + (size_t)col * ld] = acc[r];
-                    W[col + (size_t)row * ld] = acc[r];
-                }
-            }
-        }
-        __syncthreads();
-    }
-    double *scat = a.tilt_scatter + (size_t)k * d * d;
-    for (int idx = tid; idx < d * d; idx += T) scat[idx] = W[(idx % d) + (size_t)(idx / d) * ld];
-    for (int i = tid; i < d; i += T) a.tilt_mean[(size_t)k * d + i] = mean[i];
     __syncthreads();
+    for (int i = tid; i < d; i += T) {
+        double s = 0.0;
+        for (int sl = 0; sl < nsl; ++sl) s += V[i + (size_t)sl * ld];
+        mean[i] = s / (double)S;
+    }
+    __syncthreads();
+}
 
+// W = sum_s A_s B_s' over the S draws, full symmetric, MFMA f64 (method.py:417-420 / :444-446): B_s = X(s, .) - mean, and
+// A_s = B_s -- or, RW (k_reweight), B_s = (X(s, .) - mean) - dm, A_s = w_s B_s and W = n times the sum.
+template <bool RW>
+__device__ inline void draw_scatter(const double *X, long ss, long si, int S, int d, int ld, const double *mean,
+                                    const double *dm, const double *w, double n, double *W) {
+    const int tid = threadIdx.x, T = blockDim.x;
+    const int wave = tid >> 6, lane = tid & 63, nw = T >> 6;
+    const int nt = (d + 15) / 16;
+    const int ntile = nt * (nt + 1) / 2;
+    for (int tile = wave; tile < ntile; tile += nw) {
+        // unrank (ti <= tj)
+        int ti = 0, rem = tile;
+        while (rem >= nt - ti) { rem -= nt - ti; ++ti; }
+        const int tj = ti + rem;
+        const int ia = ti * 16 + (lane & 15), ib = tj * 16 + (lane & 15);
+        const double ma = ia < d ? mean[ia] : 0.0, mb = ib < d ? mean[ib] : 0.0;
+        double da = 0.0, db = 0.0;
+        if (RW) { da = ia < d ? dm[ia] : 0.0; db = ib < d ? dm[ib] : 0.0; }
+        const int kq = lane >> 4;
+        v4d acc = {0.0, 0.0, 0.0, 0.0};
+        for (int s0 = 0; s0 < S; s0 += 4) {
+            const int s = s0 + kq;
+            double av = 0.0, bv = 0.0;
+            if (s < S) {
+                if (ia < d) av = X[(long)s * ss + (long)ia * si] - ma;
+                if (ib < d) bv = X[(long)s * ss + (long)ib * si] - mb;
+                if (RW) {
+                    if (ia < d) av = (av - da) * w[s];
+                    if (ib < d) bv = bv - db;
+                }
+            }
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = ti * 16 + (lane >> 4) + 4 * r, col = tj * 16 + (lane & 15);
+            if (row < d && col < d) {
+                const double v = RW ? n * acc[r] : acc[r];
+                W[row + (size_t)col * ld] = v;
+                W[col + (size_t)row * ld] = v;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// The precision estimate from the scatter matrix in W (full) and the tilted mean, n draws' worth (k_moments: n = S;
+// k_reweight: the weighted effective sample size), and the site update dQi = Qt - Q, dri = rt - r with the flag
+// (method.py:420-465).  usable = false: the soft failure without an estimate.
+__device__ inline void precision_tail(const MomentArgs &a, int k, double *W, double *V, const double *mean, double n,
+                                      bool usable, double *red) {
+    const int d = a.d, ld = a.ld, tid = threadIdx.x, T = blockDim.x;
     double *dQ = a.dQi + (size_t)k * d * d, *dr = a.dri + (size_t)k * d;
-    bool ok;
-    if (a.prec_estim == 0) {
+    bool ok = false;
+    if (!usable) {
+    } else if (a.prec_estim == 0) {
         // 'sample': (R'R)^-1 (S-d-2)  (method.py:420-435)
         ok = block_potrf(W, d, ld);
         if (ok) {
             block_potri(W, V, d, ld);
-            const double ub = (double)(S - d - 2);
+            const double ub = n - (double)(d + 2);
             for (int i = tid; i < d; i += T) {
                 double s = 0.0;
                 for (int j = 0; j < d; ++j) s += W[i + (size_t)j * ld] * mean[j];
@@ -249,7 +252,7 @@ k_moments(MomentArgs a) {
         }
     } else {
         // 'olse' (method.py:446-451, util.py:128-194) with prior matrix P = global Q
-        const double invS = 1.0 / (double)S;
+        const double invS = 1.0 / n;
         for (int idx = tid; idx < d * d; idx += T) {
             const int i = idx % d, j = idx / d;
             if (i >= j) W[i + (size_t)j * ld] *= invS;
@@ -267,7 +270,7 @@ k_moments(MomentArgs a) {
             }
             tr = block_sum(tr, red); f2 = block_sum(f2, red);
             f2p = block_sum(f2p, red); tsp = block_sum(tsp, red);
-            const double n = (double)S, dd = (double)d, tr2 = tr * tr;
+            const double dd = (double)d, tr2 = tr * tr;
             const double alpha = 1.0 - (dd + tr2 * f2p / (f2 * f2p - tsp * tsp)) / n;   // util.py:190
             const double beta = (tsp / f2p) * (1.0 - dd / n - alpha);                   // util.py:191
             __syncthreads();
@@ -290,7 +293,178 @@ k_moments(MomentArgs a) {
         for (int i = tid; i < d; i += T) dr[i] = 0.0;
     }
     if (tid == 0) a.flags[k] = ok ? 1 : 0;
+}
+
+// Worker.tilted moment stage (method.py:410-475) for one site per block.
+__global__ void __launch_bounds__(256)
+k_moments(MomentArgs a) {
+    extern __shared__ __align__(16) double lds[];
+    __shared__ double red[16];
+    __shared__ double scal[8];
+    const int k = a.k0 + blockIdx.x;
+    const int d = a.d, ld = a.ld, tid = threadIdx.x, T = blockDim.x, S = a.S;
+    double *W, *V, *vec;
+    ws_pointers(a.ws, blockIdx.x, d, ld, lds, W, V, vec);
+    double *mean = vec;            // d
+    const double *X = a.draws + (size_t)(a.draws_site0 + blockIdx.x) * a.stride_site;
+    const long ss = a.stride_s, si = a.stride_i;
+
+    draw_mean(X, ss, si, S, d, ld, V, mean);
+    draw_scatter<false>(X, ss, si, S, d, ld, mean, nullptr, nullptr, 0.0, W);
+    double *scat = a.tilt_scatter + (size_t)k * d * d;
+    for (int idx = tid; idx < d * d; idx += T) scat[idx] = W[(idx % d) + (size_t)(idx / d) * ld];
+    for (int i = tid; i < d; i += T) a.tilt_mean[(size_t)k * d + i] = mean[i];
+    __syncthreads();
+
+    precision_tail(a, k, W, V, mean, (double)S, true, red);
     (void)scal;
+}
+
+// ------------------------------------------------------------------ reweight
+// The tilted moments of a site under a NEW cavity from draws sampled against an OLD one (include/epx.h: epx_reweight_batch
+// states the definition, reweight.py restates it in NumPy): one site per block.
+// Dynamic LDS: [the work matrices and vectors of the DensePlan, when they fit | -lr (Sp) | lw, then w (Sp) | the PSIS
+// scratch of one row (psis.h) | the tail's draw indices (M ints)].
+//   1. m0 as k_moments forms the mean;
+//   2. dOm = Om_n - Om_o into V, g = Om_n (mu_n - m0) - Om_o (mu_o - m0): both products in the same order of the same
+//      kind of terms, so that identical cavities give g == 0 exactly;
+//   3. a wave takes 16 draws at a time: Y = C dOm tile by tile of 16 columns on the matrix pipe (A: the draws' centred
+//      coordinates, B: dOm), each tile's Y(s, j) meeting c(s, j) in the lane that holds it, lr_s = sum_j c_sj (g_j - Y_sj / 2)
+//      over the column tiles in order and then over the 16 lanes of the DPP row;
+//   4. psis_smooth (psis.h) on ll = -lr by the first 16 lanes;
+//   5. lw_s, WESS = 1 / sum exp(2 lw_s), w_s = exp(lw_s), dm = sum w_s c_s;
+//   6. the weighted scatter on k_moments' tiles;  7. k_moments' estimate with n = WESS.
+// Every sum has a fixed order and nothing is accumulated atomically: the same call gives the same bytes.
+__global__ void __launch_bounds__(256)
+k_reweight(ReweightArgs ra) {
+    extern __shared__ __align__(16) double lds[];
+    __shared__ double red[16];
+    __shared__ double scal[8];
+    const MomentArgs &a = ra.m;
+    const int b = blockIdx.x, k = a.k0 + b;
+    const int d = a.d, ld = a.ld, tid = threadIdx.x, T = blockDim.x, S = a.S, M = ra.M;
+    double *W, *V, *vec;
+    ws_pointers(a.ws, b, d, ld, lds, W, V, vec);
+    double *mean = vec, *m0 = vec + ld, *g = vec + 2 * (size_t)ld, *dm = vec + 3 * (size_t)ld;
+    double *nl = lds + ra.extra_at, *w = nl + ra.Sp, *scr = w + ra.Sp;
+    int *tail_s = reinterpret_cast<int *>(scr + psis_scratch_doubles(M));
+    const double *X = a.draws + (size_t)(a.draws_site0 + b) * a.stride_site;
+    const long ss = a.stride_s, si = a.stride_i;
+    const double *Oo = ra.Om_old + (size_t)b * d * d, *On = ra.Om_new + (size_t)b * d * d;
+    const double *muo = ra.mu_old + (size_t)b * d, *mun = ra.mu_new + (size_t)b * d;
+    double *scat = a.tilt_scatter + (size_t)k * d * d, *rec = ra.rec + (size_t)b * EPX_RW_COUNT;
+
+    draw_mean(X, ss, si, S, d, ld, V, m0);
+    for (int idx = tid; idx < d * d; idx += T) V[(idx % d) + (size_t)(idx / d) * ld] = On[idx] - Oo[idx];
+    for (int i = tid; i < d; i += T) {
+        double sn = 0.0, so = 0.0;
+        for (int j = 0; j < d; ++j) {
+            sn += On[i + (size_t)j * d] * (mun[j] - m0[j]);
+            so += Oo[i + (size_t)j * d] * (muo[j] - m0[j]);
+        }
+        g[i] = sn - so;
+    }
+    __syncthreads();
+    {
+        const int wave = tid >> 6, lane = tid & 63, nw = T >> 6;
+        const int nt = (d + 15) / 16, kq = lane >> 4, c16 = lane & 15;
+        for (int s0 = wave * 16; s0 < S; s0 += nw * 16) {
+            const int sa = s0 + c16;
+            double term[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int tj = 0; tj < nt; ++tj) {
+                const int col = tj * 16 + c16;
+                v4d acc = {0.0, 0.0, 0.0, 0.0};
+                for (int k4 = 0; k4 < d; k4 += 4) {
+                    const int kk = k4 + kq;
+                    double av = 0.0, bv = 0.0;
+                    if (kk < d) {
+                        if (sa < S) av = X[(long)sa * ss + (long)kk * si] - m0[kk];
+                        if (col < d) bv = V[kk + (size_t)col * ld];
+                    }
+                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+                }
+                const double gc = col < d ? g[col] : 0.0, mc = col < d ? m0[col] : 0.0;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int sr = s0 + kq + 4 * r;
+                    const double cv = (sr < S && col < d) ? X[(long)sr * ss + (long)col * si] - mc : 0.0;
+                    term[r] += cv * (gc - 0.5 * acc[r]);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double lr = row16_sum(term[r]);
+                const int sr = s0 + kq + 4 * r;
+                if (sr < S && c16 == 0) nl[sr] = -lr;
+            }
+        }
+    }
+    __syncthreads();
+    int bad = 0;
+    for (int s = tid; s < S; s += T) bad |= isfinite(nl[s]) ? 0 : 1;
+    if (__syncthreads_or(bad)) {
+        // a ratio that is not finite: no record, no update
+        for (int idx = tid; idx < d * d; idx += T) { scat[idx] = NAN; a.dQi[(size_t)k * d * d + idx] = 0.0; }
+        for (int i = tid; i < d; i += T) { a.tilt_mean[(size_t)k * d + i] = NAN; a.dri[(size_t)k * d + i] = 0.0; }
+        if (tid < EPX_RW_COUNT) rec[tid] = NAN;
+        if (tid == 0) a.flags[k] = 0;
+        return;
+    }
+    if (tid < 16) {
+        const PsisFit f = psis_smooth(nl, S, M, ra.mfit, scr, tid, tail_s);
+        if (tid == 0) {
+            scal[0] = f.mx; scal[1] = f.khat; scal[2] = f.u_lr; scal[3] = f.lse;
+            scal[4] = (double)f.u_at; scal[5] = f.smoothed ? 1.0 : 0.0;
+        }
+    }
+    __syncthreads();
+    const double mx = scal[0], khat = scal[1], u_lr = scal[2], lse = scal[3];
+    const int u_at = (int)scal[4];
+    const bool smoothed = scal[5] != 0.0;
+    for (int s = tid; s < S; s += T) {
+        const double lr = -nl[s] - mx;
+        const bool in_tail = smoothed && ((lr > u_lr) | ((lr == u_lr) & (s > u_at)));
+        if (!in_tail) w[s] = lr - lse;
+    }
+    if (smoothed) {
+        const double *tail_x = scr + psis_tail_pad(M);
+        for (int j = tid; j < M; j += T) w[tail_s[j]] = tail_x[j] - lse;
+    }
+    __syncthreads();
+    double s2 = 0.0;
+    for (int s = tid; s < S; s += T) s2 += exp(2.0 * w[s]);
+    const double n = 1.0 / block_sum(s2, red);
+    __syncthreads();
+    for (int s = tid; s < S; s += T) w[s] = exp(w[s]);
+    __syncthreads();
+    {
+        // dm = sum_s w_s c_s : thread = (coordinate, slice), the slices combined in order (V is free again)
+        int nsl = T / d;
+        if (nsl > d) nsl = d;
+        if (nsl < 1) nsl = 1;
+        for (int idx = tid; idx < d * nsl; idx += T) {
+            const int i = idx % d, sl = idx / d;
+            const double mi = m0[i];
+            double s = 0.0;
+            for (int t = sl; t < S; t += nsl) s += w[t] * (X[(long)t * ss + (long)i * si] - mi);
+            V[i + (size_t)sl * ld] = s;
+        }
+        __syncthreads();
+        for (int i = tid; i < d; i += T) {
+            double s = 0.0;
+            for (int sl = 0; sl < nsl; ++sl) s += V[i + (size_t)sl * ld];
+            dm[i] = s;
+            mean[i] = m0[i] + s;
+        }
+        __syncthreads();
+    }
+    draw_scatter<true>(X, ss, si, S, d, ld, m0, dm, w, n, W);
+    for (int idx = tid; idx < d * d; idx += T) scat[idx] = W[(idx % d) + (size_t)(idx / d) * ld];
+    for (int i = tid; i < d; i += T) a.tilt_mean[(size_t)k * d + i] = mean[i];
+    if (tid == 0) { rec[EPX_RW_KHAT] = khat; rec[EPX_RW_WESS] = n; }
+    __syncthreads();
+    const bool usable = a.prec_estim != 0 || n - (double)(d + 2) > 0.0;
+    precision_tail(a, k, W, V, mean, n, usable, red);
 }
 
 // ------------------------------------------------------- site sums (2 stage)

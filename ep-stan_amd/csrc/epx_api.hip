@@ -767,6 +767,10 @@ static int run_sampler(epx_ctx *c, int k0, int count, const int64_t *seeds, cons
     if (hook && !q.on) return fail("epx_sample_piece: the checkpoint records / tree stacks of the pieced launch could not be allocated");
     if (q.on) n_lead = 0;
     HIPCHK(c->stack.grow(stack_elems));
+    if (c->reuse_on) {      // epx_set_draw_reuse: room for the cavities this call samples against
+        HIPCHK(c->drawn_Om.grow((size_t)c->K * c->d * c->d));
+        HIPCHK(c->drawn_mu.grow((size_t)c->K * c->d));
+    }
     if (q.on) HIPCHK(c->dyn_words.grow(2 * (size_t)c->K));
     if (ts) HIPCHK(c->trace.grow(trace_elems));
 #ifdef EPX_STAMPS
@@ -815,6 +819,13 @@ static int run_sampler(epx_ctx *c, int k0, int count, const int64_t *seeds, cons
     if (n_lead > 0) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
     if (rc != 0) return fail("NUTS kernel launch failed (%d: %s)", rc, rc > 0 ? hipGetErrorString((hipError_t)rc) : "unsupported shape");
     HIPCHK(hipEventRecord(c->ev1, c->stream));
+    c->snap_count = 0;
+    if (c->reuse_on) {
+        const size_t d = c->d, dd = d * d;
+        HIPCHK(hipMemcpyAsync(c->drawn_Om + k0 * dd, c->cav_Om + k0 * dd, count * dd * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->drawn_mu + k0 * d, c->cav_mu + k0 * d, count * d * 8, hipMemcpyDeviceToDevice, c->stream));
+        c->snap_k0 = k0; c->snap_count = count;
+    }
     // 7. epilogue: site statistics, carry history, the hand-off error flag, the hook's records, the time
     RhatArgs ra;
     ra.k0 = k0; ra.chains = o.chains; ra.nkeep = nkeep; ra.P = c->P;
@@ -852,7 +863,7 @@ static int run_sampler(epx_ctx *c, int k0, int count, const int64_t *seeds, cons
     }
     if (herr) {
         HIPCHK(hipMemset(c->err_flag, 0, sizeof(int)));
-        c->drawn_count = 0;
+        c->drawn_count = 0; c->snap_count = 0;
         return fail("sampler: a hand-off between the waves of a chain timed out (code %d); the draws of this call are void", herr);
     }
     if (elapsed_ms) {
@@ -932,6 +943,74 @@ int epx_moments_batch(epx_ctx *c, int k0, int count, const double *samples, int 
     if (launch_moments(c, k0, count, c->inj, 0, (long)S * c->d, 1, S, S, prec_estim)) return -1;
     if (fetch_flags(c, k0, count, posdef)) return -1;
     c->nsamp = S;
+    return 0;
+}
+
+int epx_set_draw_reuse(epx_ctx *c, int on) {
+    if (!c) return fail("null context");
+    c->reuse_on = on ? 1 : 0;
+    if (!on) c->snap_count = 0;
+    return 0;
+}
+
+int epx_reweight_batch(epx_ctx *c, int k0, int count, int prec_estim, const double *theta, int S,
+                       const double *Om_old, const double *mu_old, uint8_t *posdef, double *out, double *elapsed_ms) {
+    CTX(c);
+    if (check_range(c, k0, count)) return -1;
+    if (theta && (!Om_old || !mu_old)) return fail("epx_reweight_batch: draws of the caller need Om_old and mu_old, the cavity they were sampled against");
+    DrawSource src;
+    if (draw_source(c, "epx_reweight_batch", k0, count, theta, S, nullptr, &src)) return -1;
+    S = src.S;
+    if (check_moments(c, S, prec_estim)) return -1;
+    // the LDS plan: [work matrices and vectors (DensePlan), when they fit beside the rest | -lr (Sp) | w (Sp) | PSIS scratch of
+    // one row | the tail's draw indices (M ints)]
+    const size_t d = c->d;
+    const DensePlan p(c->d);
+    ReweightArgs a;
+    a.M = psis_tail_length(S); a.mfit = psis_fit_points(a.M); a.Sp = (S + 1) / 2 * 2;
+    const size_t extra = 2 * (size_t)a.Sp + psis_scratch_doubles(a.M) + psis_tail_pad(a.M) / 2 + 1;
+    if (a.mfit > PSIS_FIT_MAX || extra * 8 + 1024 > LDS_CAP)
+        return fail("epx_reweight_batch: S = %d draws: the ratios and weights of a site do not fit the LDS", S);
+    const bool in_lds = (p.slot + extra) * 8 + 1024 <= LDS_CAP;
+    if (!theta && (!c->drawn_Om || k0 < c->snap_k0 || k0 + count > c->snap_k0 + c->snap_count))
+        return fail("epx_reweight_batch: no record of the cavity the draws of sites [%d,%d) were sampled against: switch "
+                    "epx_set_draw_reuse on before the sampling call", k0, k0 + count);
+    HIPCHK(c->dense_ws.grow(in_lds ? 0 : p.slot * (size_t)count));
+    HIPCHK(c->rw_out.grow((size_t)count * EPX_RW_COUNT));
+    if (theta) HIPCHK(c->rw_old.grow((size_t)count * (d * d + d)));
+    a.extra_at = in_lds ? (int)p.slot : 0;
+    const size_t lds = ((in_lds ? p.slot : 0) + extra) * 8;
+    if (set_lds(k_reweight, lds)) return -1;
+    MomentArgs &m = a.m;
+    m.k0 = k0; m.d = c->d; m.ld = p.ld; m.S = S; m.prec_estim = prec_estim;
+    m.ws.use_lds = in_lds; m.ws.global = in_lds ? nullptr : c->dense_ws.p;
+    m.draws_site0 = 0; m.stride_site = (long)S * c->P; m.stride_s = c->P; m.stride_i = 1;
+    m.Q = c->Q; m.r = c->r; m.dQi = c->dQi; m.dri = c->dri;
+    m.tilt_mean = c->tilt_mean; m.tilt_scatter = c->tilt_scatter; m.flags = c->flags;
+    a.Om_new = c->cav_Om + k0 * d * d; a.mu_new = c->cav_mu + k0 * d;
+    a.rec = c->rw_out;
+    StreamSync sync{c->stream};
+    if (upload_draws(c, src, &m.draws)) return -1;
+    if (theta) {
+        HIPCHK(hipMemcpyAsync(c->rw_old, Om_old, count * d * d * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->rw_old + count * d * d, mu_old, count * d * 8, hipMemcpyHostToDevice, c->stream));
+        a.Om_old = c->rw_old; a.mu_old = c->rw_old + count * d * d;
+    } else {
+        a.Om_old = c->drawn_Om + k0 * d * d; a.mu_old = c->drawn_mu + k0 * d;
+    }
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(k_reweight, dim3(count), dim3(256), lds, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    if (posdef) HIPCHK(hipMemcpyAsync(posdef, c->flags + k0, count, hipMemcpyDeviceToHost, c->stream));
+    if (out) HIPCHK(hipMemcpyAsync(out, c->rw_out, (size_t)count * EPX_RW_COUNT * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sync.finish()) return -1;
+    c->nsamp = S;
+    if (elapsed_ms) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *elapsed_ms = ms;
+    }
     return 0;
 }
 

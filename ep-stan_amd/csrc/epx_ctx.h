@@ -104,6 +104,10 @@ struct epx_ctx {
     DevBuf<double> Qi, ri, Qi2, ri2, dQi, dri;
     DevBuf<double> cav_Om, cav_mu;
     DevBuf<double> tilt_mean, tilt_scatter;
+    // epx_set_draw_reuse: the cavities the sites of the last sampling call were sampled against (K x d x d, K x d, no
+    // padding), the sites they cover, and the buffers of epx_reweight_batch: the caller's old cavities, the records
+    int reuse_on = 0, snap_k0 = 0, snap_count = 0;
+    DevBuf<double> drawn_Om, drawn_mu, rw_old, rw_out;
     DevBuf<uint8_t> flags;
     DevBuf<int> iflags;             // [4]
     DevBuf<double> packed, partial; // sums

@@ -39,6 +39,17 @@ struct MomentArgs {
     uint8_t *flags;
 };
 
+// k_reweight (dense.hip; include/epx.h: epx_reweight_batch): block b takes site m.k0 + b of the context
+struct ReweightArgs {
+    MomentArgs m;                      // draws, sizes, the global approximation and the outputs as k_moments takes them
+    const double *Om_old, *mu_old;     // the cavity the draws were sampled against: block b at + b d d, + b d (column-major)
+    const double *Om_new, *mu_new;     // the cavity now, likewise
+    double *rec;                       // count x EPX_RW_COUNT
+    int M, mfit;                       // psis_tail_length(S), psis_fit_points(M)
+    int Sp;                            // S rounded up to even
+    int extra_at;                      // doubles of dynamic LDS in front of [-lr (Sp) | w (Sp) | PSIS scratch | tail draws (M ints)]
+};
+
 struct SumArgs {
     int K, d, len, nslice;
     const double *Qi, *ri, *dQi, *dri;
@@ -230,6 +241,7 @@ __global__ void k_draw_diag(DiagArgs a);
 
 __global__ void k_cavity(CavityArgs a);
 __global__ void k_moments(MomentArgs a);
+__global__ void k_reweight(ReweightArgs a);
 __global__ void k_site_sums_partial(SumArgs a);
 __global__ void k_site_sums_final(SumArgs a);
 __global__ void k_global(GlobalArgs a);

@@ -1,6 +1,8 @@
 // Pareto-smoothed importance sampling of ONE row's leave-one-out ratios (include/epx.h, enum epx_loo, states the
 // definition; loo.psis_host is the NumPy statement): from the S log-likelihoods ll_s of a row under the draws of its site
-// to ELPD, KHAT and WESS.  Used by k_loo and k_psis_rows (predict.hip).
+// to ELPD, KHAT and WESS.  Used by k_loo and k_psis_rows (predict.hip): psis_row = psis_smooth (the order, the fit, the
+// smoothed tail and the normaliser) + the reductions.  k_reweight (dense.hip) calls psis_smooth alone on the log ratios of
+// two cavities and forms every draw's own weight from what it leaves.
 //
 // A row is worked on by the 16 lanes of one DPP row (lane c = lane & 15 takes the draws s = c, c + 16, ...), all of them
 // active, every argument the same in the 16 lanes; four rows share a wave.  Every sum is a lane's own terms in
@@ -83,9 +85,15 @@ __device__ inline bool psis_row_finite(const double *ll, int S, int c) {
 
 struct PsisOut { double elpd, khat, wess; };
 
+// What the smoothing (steps 1-7) leaves for whoever forms sums over the smoothed weights: draw s lies in the tail exactly
+// when smoothed and (lr_s, s) > (u_lr, u_at), lr_s = -ll_s - mx; the tail's smoothed lr, ascending, are then in the row's
+// scratch at scr + psis_tail_pad(M) and its ll at scr; lw = lr - lse.
+struct PsisFit { double mx, khat, u_lr, u_ll, lse; int u_at; bool smoothed; };
+
 // ll: the row's S FINITE log-likelihoods (LDS or global); M, mfit: psis_tail_length(S), psis_fit_points(M); scr: the row's
-// psis_scratch_doubles(M) doubles of LDS
-__device__ inline PsisOut psis_row(const double *ll, int S, int M, int mfit, double *scr, int c) {
+// psis_scratch_doubles(M) doubles of LDS; tail_s: NULL, or M ints of LDS that get the draw index of every tail member in
+// rank order (k_reweight, dense.hip: it needs every draw's own weight)
+__device__ inline PsisFit psis_smooth(const double *ll, int S, int M, int mfit, double *scr, int c, int *tail_s) {
     const int Mp = psis_tail_pad(M), Cp = psis_cand_cap(M);
     double *tail_ll = scr, *tail_x = scr + Mp, *cand_v = tail_x;
     int *cand_s = reinterpret_cast<int *>(scr + Mp + Cp);
@@ -95,7 +103,7 @@ __device__ inline PsisOut psis_row(const double *ll, int S, int M, int mfit, dou
     for (int s = c; s < S; s += 16) mx = fmax(mx, -ll[s]);
     mx = row16_max(mx);
 
-    PsisOut o;
+    PsisFit o;
     o.khat = INFINITY;
     bool smoothed = false;
     double u_lr = INFINITY, u_ll = -mx;                   // not smoothed: nothing lies behind u; lr = 0 stands for the rest
@@ -150,8 +158,10 @@ __device__ inline PsisOut psis_row(const double *ll, int S, int M, int mfit, dou
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    if (cnt[i] < M) tail_ll[M - 1 - cnt[i]] = ll[si[i]];
-                    else if (cnt[i] == M) { uslot[0] = ll[si[i]]; uslot[1] = (double)si[i]; }
+                    if (cnt[i] < M) {
+                        tail_ll[M - 1 - cnt[i]] = ll[si[i]];
+                        if (tail_s) tail_s[M - 1 - cnt[i]] = si[i];
+                    } else if (cnt[i] == M) { uslot[0] = ll[si[i]]; uslot[1] = (double)si[i]; }
                 }
             }
         } else {
@@ -177,8 +187,10 @@ __device__ inline PsisOut psis_row(const double *ll, int S, int M, int mfit, dou
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    if (cnt[i] < M) tail_ll[M - 1 - cnt[i]] = ll[si[i]];
-                    else if (cnt[i] == M) { uslot[0] = ll[si[i]]; uslot[1] = (double)si[i]; }
+                    if (cnt[i] < M) {
+                        tail_ll[M - 1 - cnt[i]] = ll[si[i]];
+                        if (tail_s) tail_s[M - 1 - cnt[i]] = si[i];
+                    } else if (cnt[i] == M) { uslot[0] = ll[si[i]]; uslot[1] = (double)si[i]; }
                 }
             }
         }
@@ -247,7 +259,20 @@ __device__ inline PsisOut psis_row(const double *ll, int S, int M, int mfit, dou
     }
     if (smoothed)
         for (int j = c; j < M; j += 16) s1 += exp_d(tail_x[j] - top);
-    const double lse = top + log(row16_sum(s1));
+    o.lse = top + log(row16_sum(s1));
+    o.mx = mx; o.u_lr = u_lr; o.u_ll = u_ll; o.u_at = u_at; o.smoothed = smoothed;
+    return o;
+}
+
+__device__ inline PsisOut psis_row(const double *ll, int S, int M, int mfit, double *scr, int c) {
+    const PsisFit f = psis_smooth(ll, S, M, mfit, scr, c, nullptr);
+    const int Mp = psis_tail_pad(M);
+    const double *tail_ll = scr, *tail_x = scr + Mp;
+    const double mx = f.mx, u_lr = f.u_lr, u_ll = f.u_ll, lse = f.lse;
+    const int u_at = f.u_at;
+    const bool smoothed = f.smoothed;
+    PsisOut o;
+    o.khat = f.khat;
     // 8., 9. ELPD = logsumexp(lw + ll), WESS = 1 / sum exp(2 lw)
     double me = ((smoothed ? u_lr : 0.0) - lse) + u_ll;
     if (smoothed) {

@@ -261,6 +261,36 @@ class HipEngine(object):
                                          flags.ctypes.data_as(_lib.c_uint8_p)))
         return flags.astype(bool)
 
+    # ---- reuse of the draws across iterations (include/epx.h: epx_reweight_batch; reweight.py)
+    def set_draw_reuse(self, on):
+        """On: every sampling call keeps the cavities it sampled against, for `reweight_batch()` without `theta`."""
+        check(self.lib.epx_set_draw_reuse(self.ctx, 1 if on else 0))
+
+    def reweight_batch(self, prec_estim, k0=0, count=None, theta=None, Om_old=None, mu_old=None):
+        """The tilted moments and site updates of the sites k0..k0+count under the context's CURRENT cavities from draws
+        sampled against older ones, by Pareto-smoothed importance sampling; the results lie where `tilted_batch` leaves
+        them.  The draws and their cavities are those of the last sampling call (`set_draw_reuse(True)` before it), or
+        `theta` (count, S, P) with `Om_old` (count, d, d) and `mu_old` (count, d).  Returns (posdef bool[count], rec
+        (count, 2): columns reweight.RW_KHAT, RW_WESS, kernel ms)."""
+        count = self.K - k0 if count is None else count
+        theta, S = self._injected(theta, count)
+        if Om_old is not None:
+            Om_old = np.asarray(Om_old, dtype=np.float64)
+            if Om_old.shape != (count, self.d, self.d):
+                raise ValueError('Om_old: (count, d, d)')
+            Om_old = np.ascontiguousarray(Om_old.transpose(0, 2, 1))        # column-major per site
+        if mu_old is not None:
+            mu_old = np.ascontiguousarray(mu_old, dtype=np.float64)
+            if mu_old.shape != (count, self.d):
+                raise ValueError('mu_old: (count, d)')
+        flags = np.zeros(max(count, 0), dtype=np.uint8)
+        rec = np.zeros((max(count, 0), 2))
+        ms = ctypes.c_double()
+        check(self.lib.epx_reweight_batch(self.ctx, int(k0), int(count), PREC_ESTIM_IDS.get(prec_estim, prec_estim),
+                                          dptr(theta), int(S), dptr(Om_old), dptr(mu_old),
+                                          flags.ctypes.data_as(_lib.c_uint8_p), dptr(rec), ctypes.byref(ms)))
+        return flags.astype(bool), rec, ms.value
+
     def get_tilted(self, k):
         Mat = np.empty((self.d, self.d), order='F')
         vec = np.empty(self.d)

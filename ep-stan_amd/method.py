@@ -35,6 +35,7 @@ from . import engine as _engine
 from . import loo as _loo
 from . import mix_pred as _mix_pred
 from . import quantiles as _quantiles
+from . import reweight as _reweight
 from . import site_params as _site_params
 from .seeds import MAX_UINT, run_seeds, stan_seed, stan_seeds
 from .util import invert_normal_params
@@ -263,6 +264,27 @@ class Worker(object):
         dri[...] = dr
         return ok
 
+    def tilted_reuse(self, dQi, dri):
+        """`tilted` without sampling: the tilted moments under the current cavity from the draws of the site's last
+        sampling call, by Pareto-smoothed importance sampling from the cavity they were sampled against (reweight.py;
+        include/epx.h: epx_reweight_batch).  Phase rules and outputs of `tilted`; returns (pos_def, khat, wess) -- whether
+        to trust them is the caller's decision (`reweight.reuse_ok`).  The engine must have kept that cavity:
+        `set_draw_reuse(True)` before the sampling call (`Master.run(reuse=...)` does it); it raises otherwise."""
+        if self.phase != 1:
+            raise RuntimeError('Cavity has to be calculated before tilted.')
+        if self._eng is None:
+            raise RuntimeError('this site belongs to another rank')
+        if self.Q is not None:
+            self._eng.set_global(self.Q, self.r)
+        flags, rec, ms = self._eng.reweight_batch(self._cur_estim(), k0=self._k, count=1)
+        ok = bool(flags[0])
+        self.last_time = ms * 1e-3
+        self._finish_tilted(ok)
+        dQ, dr = self._eng.get_site(_engine.DQI, self._k)
+        dQi[...] = dQ
+        dri[...] = dr
+        return ok, float(rec[0, _reweight.RW_KHAT]), float(rec[0, _reweight.RW_WESS])
+
     def diagnostics(self):
         """Per-coordinate diagnostics of the draws of this site's last `tilted` on a stand-alone Worker's own engine:
         the (P, DG_COUNT) record of `diagnostics.diagnostics_host` (columns DG_MEAN, DG_VAR, DG_RHAT, DG_ESS, DG_MCSE,
@@ -484,6 +506,7 @@ class Master(object):
         self.pass_log = []                  # passes over the site rows of every sampling launch (per site)
         self.team_pass_log = []             # layout 7: passes the row team made per launch (all sites), else None
         self.sweep_log = []                 # results of `run(..., sweep=...)`, one dict per iteration
+        self.reuse_log = []                 # `run(..., reuse=...)`: one dict per iteration of the last such run (this rank)
         self.df_log = []                    # damping factor accepted in every iteration
         self.othertime_log = []             # host time of every update phase (this rank)
         device = gpu['device']
@@ -1173,7 +1196,7 @@ class Master(object):
         return tuple(out) if as_tuple else out
 
     def run(self, niter, calc_moments=True, save_last_param=None, verbose=True,
-            return_analytics=False, seed=None, sweep=None):
+            return_analytics=False, seed=None, sweep=None, reuse=None):
         """Run the distributed EP algorithm (method.py:899-1247).
 
         Returns `info`, optionally followed by `(m_phi_s, cov_phi_s)` and
@@ -1185,15 +1208,33 @@ class Master(object):
 
         `sweep` (not in the reference's `run`; it is the body of experiment/find_damp.py): a dict
         `damps, m_target, S_target[, samp_target]`; every iteration scores these damping factors
-        before its own damped update and appends the result to `self.sweep_log`."""
+        before its own damped update and appends the result to `self.sweep_log`.
+
+        `reuse` (not in the reference): True, or a dict with `k_max` and / or `min_ess` (`reweight.reuse_ok`).  From the
+        second iteration on every rank first reweights the draws of its last sampling launch to the current cavities
+        (`HipEngine.reweight_batch`); if every local site passes `reuse_ok`, the iteration takes its tilted moments from
+        the reweighting and launches no sampler, otherwise all local sites sample as without `reuse`.  The decision is
+        per rank.  `self.reuse_log` gets one dict per iteration: `reused, n_ok, khat_max` (the largest smoothed k-hat),
+        `wess_min_frac` (the smallest WESS / S), `ms` (the reweighting kernel).  In a reused iteration `stimes` is the
+        reweighting's time and `msteps`, `mrhats` keep the values of the last sampled one."""
         if niter < 1:
             if verbose:
                 print("Nothing to do here as provided arg. `niter` is {}".format(niter))
             return self._ret(self.INFO_OK, calc_moments, return_analytics,
                              (None, None), (None, None, None))
 
-        seeds = run_seeds(seed, niter, self.K)                    # :956-960
+        seeds = run_seeds(seed, niter, self.K)                    # :956-960 (per iteration, drawn up front)
         eng = self.engine
+        reuse_on = reuse is not None and reuse is not False
+        if reuse_on:
+            policy = {} if reuse is True else dict(reuse)
+            if set(policy) - {'k_max', 'min_ess'}:
+                raise ValueError("`reuse`: True or a dict with 'k_max' and / or 'min_ess'")
+            if self._sample_injector is not None:
+                raise ValueError('`reuse` needs the draws of the device sampler')
+            eng.set_draw_reuse(True)
+            self.reuse_log = []
+        have_draws = False              # a sampling launch of THIS run left draws and their cavities on the device
         lo, hi, K = self.k_lo, self.k_hi, self.K
         local_workers = self.workers[lo:hi]
 
@@ -1225,7 +1266,23 @@ class Master(object):
             sseeds = stan_seeds(seeds[cur_iter, lo:hi])             # :342-346
             estim = w0._cur_estim()
             self._draws_injected = self._sample_injector is not None
-            if self._sample_injector is not None:
+            reused = False
+            if reuse_on:
+                entry = dict(reused=False, n_ok=0, khat_max=float('nan'), wess_min_frac=float('nan'), ms=0.0)
+                if have_draws:
+                    rw_flags, rec, rw_ms = eng.reweight_batch(estim)
+                    khat, wess, S_draws = rec[:, _reweight.RW_KHAT], rec[:, _reweight.RW_WESS], eng.num_draws()
+                    site_ok = _reweight.reuse_ok(khat, wess, S_draws, **policy)
+                    reused = bool(np.all(site_ok))
+                    entry = dict(reused=reused, n_ok=int(np.sum(site_ok)),
+                                 khat_max=float(np.max(np.where(np.isposinf(khat), -np.inf, khat))),
+                                 wess_min_frac=float(np.min(wess)) / S_draws, ms=rw_ms)
+                self.reuse_log.append(entry)
+            if reused:
+                posdefs_l = rw_flags
+                tl = np.full(self.K_local, rw_ms * 1e-3)
+                ml, rl = last_ml, last_rl
+            elif self._sample_injector is not None:
                 posdefs_l, tl, ml, rl = self._tilted_injected(sseeds, estim)
             else:
                 opts = w0._sampler_opts()
@@ -1263,6 +1320,8 @@ class Master(object):
                             eng.set_piece_queue(0)
                 tl = np.full(self.K_local, ms * 1e-3)
                 ml, rl = stats[:, 0], stats[:, 1]
+                last_ml, last_rl = ml, rl
+                have_draws = not np.any(stats[:, 7] > 0)            # (a voided site's draws are its initial points)
             nsamp = eng.get_tilted(0)[2]
             for j, w in enumerate(local_workers):
                 w.stan_params['seed'] = int(sseeds[j])

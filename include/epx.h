@@ -193,6 +193,38 @@ int epx_moments_batch(epx_ctx *ctx, int k0, int count, const double *samples, in
 /* Worker.vec (tilted mean) and Worker.Mat (unnormalised scatter C'C) of site k
  * after tilted (phase 2); nsamp out (method.py:408) */
 int epx_get_tilted(epx_ctx *ctx, int k, double *Mat, double *vec, int *nsamp);
+/*
+ * Reuse of the tilted draws across EP iterations (not in the reference).  Between two iterations a site's tilted
+ * distribution changes only through its Gaussian cavity, so the tilted moments under the NEW cavity N(mu_n, Om_n^-1) follow
+ * from draws sampled against the OLD one N(mu_o, Om_o^-1) by Pareto-smoothed importance sampling, without a likelihood
+ * evaluation.  Per site, with the S draws' first d coordinates phi_s and the context's global (Q, r):
+ *   1. m0 = (1/S) sum_s phi_s (in the order of the moment stage), c_s = phi_s - m0;
+ *   2. dOm = Om_n - Om_o, g = Om_n (mu_n - m0) - Om_o (mu_o - m0), lr_s = g'c_s - c_s'dOm c_s / 2: the log ratio of the
+ *      two cavity densities at phi_s up to a constant, centred at m0; identical cavities give lr_s == 0.0 exactly;
+ *   3. a lr_s that is not finite: the site's record, mean and scatter are NaN, its flag 0 and dQi = dri = 0;
+ *   4. else PSIS as `enum epx_loo` defines it on ll = -lr (tail length, order by (lr, s), Zhang-Stephens fit, cap at 0):
+ *      the normalised log weights lw_s, KHAT (+inf exactly when the tail is not smoothed: fewer than 5 tail draws, a
+ *      degenerate tail or a non-finite fit; the weights are then the plain normalised ratios), WESS = 1 / sum exp(2 lw_s);
+ *   5. w_s = exp(lw_s), dm = sum w_s c_s, tilted mean m0 + dm, n = WESS (a double),
+ *      tilted scatter n sum w_s (c_s - dm)(c_s - dm)': with equal weights the mean and scatter of the moment stage;
+ *   6. the precision estimate of the moment stage with S replaced by n -- EPX_PREC_SAMPLE: inv(scatter) (n - d - 2),
+ *      EPX_PREC_OLSE: on scatter / n with n -- then dQi = Qt - Q, dri = rt - r.  The site fails softly (flag 0, dQi = dri =
+ *      0) when the Cholesky fails, and under EPX_PREC_SAMPLE when n - d - 2 <= 0.  nsamp reports S.
+ * The results go where epx_tilted_batch leaves them (tilted mean / scatter, dQi, dri, flags, nsamp).
+ *
+ * epx_set_draw_reuse(ctx, 1): every sampling call from then on keeps a copy of the cavities of the sites it sampled, so
+ * that epx_reweight_batch with theta == NULL can reweight the draws of the last sampling call to the context's current
+ * cavities.  Off (the default), a sampling call queues nothing extra.
+ * epx_reweight_batch: theta == NULL: the draws and the cavity copy of the last sampling call; else theta (count, S, P)
+ * row-major with Om_old (count, d, d) column-major and mu_old (count, d), all three required.  The new cavity is the
+ * context's current one (epx_cavity_batch / epx_cavity_site / the accepted trial).  posdef[count] out (may be NULL);
+ * out: count x EPX_RW_COUNT (may be NULL); elapsed_ms (may be NULL): device time of the kernel.
+ */
+enum epx_reweight { EPX_RW_KHAT = 0, EPX_RW_WESS, EPX_RW_COUNT };
+int epx_set_draw_reuse(epx_ctx *ctx, int on);
+int epx_reweight_batch(epx_ctx *ctx, int k0, int count, int prec_estim, const double *theta, int S,
+                       const double *Om_old, const double *mu_old, uint8_t *posdef,
+                       double *out /* count x EPX_RW_COUNT */, double *elapsed_ms);
 /* phi draws of site k in the reference's layout: (S, dphi) F-order, chains
  * concatenated chain-major (util.py:475-484); all sampled coordinates with
  * npar_out = 1: (S, P) F-order. */
