@@ -25,11 +25,13 @@ __all__ = ['Worker', 'Master']
 import os
 import sys
 import time
+from collections import namedtuple
 
 import numpy as np
 from numpy.linalg import LinAlgError
 
 from . import diagnostics as _diagnostics
+from . import dispatch as _dispatch
 from . import dist as _dist
 from . import engine as _engine
 from . import loo as _loo
@@ -308,8 +310,10 @@ class Worker(object):
         self.data['mu_phi'] = v
         self.data['Omega_phi'] = M.T
 
-    def _finish_tilted(self, ok):
-        self.nsamp = self._eng.get_tilted(self._k)[2]
+    def _finish_tilted(self, ok, nsamp=None):
+        """The bookkeeping behind a tilted step (method.py:440-475).  `nsamp`: the draws behind the moments where the
+        caller has fetched them for a whole batch (`Master.run`)."""
+        self.nsamp = self._eng.get_tilted(self._k)[2] if nsamp is None else nsamp
         if self.prec_estim_skip > 0:
             self.prec_estim_skip -= 1
         if ok:
@@ -420,6 +424,28 @@ def _damping_schedule(df0, K):
                              "in (0,1]")
         return lambda i, _v=df0: _v
     return df0
+
+
+# ---------------------------------------------------------------------------------------------
+# what the stages of Master.run hand each other
+
+# A tilted step over a rank's sites: per site whether the update stands, the time (s), mean step size and largest R-hat
+# reported for it; `reuse_entry`: the step's entry of `Master.reuse_log` (None: draw reuse is off).
+_Tilted = namedtuple('_Tilted', 'posdefs times msteps mrhats reuse_entry')
+
+
+class _Reuse(object):
+    """Draw reuse inside ONE `Master.run` call: the policy (keywords of `reweight.reuse_ok`), whether the call's last
+    sampling launch left usable draws and their cavities on the device, and the step sizes and R-hats of that launch,
+    which a reused iteration reports again."""
+
+    def __init__(self, policy):
+        self.policy = policy
+        self.have_draws = False
+        self.msteps = self.mrhats = None
+
+    def keep(self, msteps, mrhats, usable):
+        self.msteps, self.mrhats, self.have_draws = msteps, mrhats, usable
 
 
 class Master(object):
@@ -1098,41 +1124,34 @@ class Master(object):
         out = np.ascontiguousarray(full[:-1, :].T).reshape(self.K, Pmax, C)
         return _diagnostics.summarise(out, np.rint(full[-1, :]).astype(np.int64))
 
-    # a site whose slowest chain took more than this fraction of the iteration's slowest chain is
-    # scheduled one workgroup per chain next time (measured leapfrog: 5.6 vs 10.3 us at D=32, n=500)
-    LEAD_FRACTION = 0.4
+    # ---- dispatch of the sampling launches: the policy is dispatch.py's, these are its two knobs and what it needs to
+    # know of this rank
+    LEAD_FRACTION = _dispatch.LEAD_FRACTION
+    PIECES_PER_SITE = int(os.environ.get('EPX_PIECES_PER_SITE', '16'))     # (the environment variable: A/B runs only)
 
     @classmethod
     def _site_schedule(cls, passes, chain_leapfrogs, n_cu=256):
-        """Dispatch order and number of lead sites for the next sampling launch from the work of
-        this one.  A launch ends with its slowest chain, and which sites hold the slow chains is
-        stable from one EP iteration to the next (a property of the site's posterior geometry:
-        measured rank correlation 0.96-0.98 at C3), so the sites within LEAD_FRACTION of the
-        slowest come first, ordered by their slowest chain, and run at the shorter leapfrog of
-        one workgroup per chain (engine.set_site_split); the others follow longest-first."""
-        chain_leapfrogs = np.asarray(chain_leapfrogs)
-        site_max = chain_leapfrogs.max(axis=1)
-        lead = np.where(site_max > cls.LEAD_FRACTION * site_max.max())[0]
-        # no tail to speak of: many sites near the slowest, or enough work to keep every CU (one
-        # site, i.e. up to 4 chains, each) busy for most of the slowest chain's run anyway
-        busy = site_max.sum() / n_cu
-        if lead.size * 4 > site_max.size or busy > 0.7 * site_max.max():
-            lead = lead[:0]
-        lead = lead[np.argsort(-site_max[lead], kind='stable')]
-        rest = np.setdiff1d(np.arange(site_max.size), lead)
-        rest = rest[np.argsort(-np.asarray(passes)[rest], kind='stable')]
-        return np.concatenate((lead, rest)).astype(np.int32), int(lead.size)
-
-    PIECES_PER_SITE = int(os.environ.get('EPX_PIECES_PER_SITE', '16'))     # (the environment variable: A/B runs only)
+        return _dispatch.site_schedule(passes, chain_leapfrogs, n_cu, cls.LEAD_FRACTION)
 
     def _one_workgroup_per_cu(self):
-        """The resident sampler keeps a site's rows (padded to 16 / 32 columns) in LDS: above half of the 160 KB
-        only one workgroup fits a CU; the streaming sampler (D > 32, or rows beyond the LDS) always fills it.  Then
-        a pieced launch (one resident workgroup per CU, looping over pieces) loses nothing to occupancy."""
-        n_max = int(np.max(np.diff(self.k_lim[self.k_lo:self.k_hi + 1])))
-        if self.D > 32:
-            return True
-        return n_max * (16 if self.D <= 16 else 32) * 8 > 80 * 1024
+        return _dispatch.one_workgroup_per_cu(self.D, int(np.max(np.diff(self.k_lim[self.k_lo:self.k_hi + 1]))))
+
+    def _dispatch_rank(self):
+        eng = self.engine
+        return _dispatch.Rank(balance=self.balance_sites, has_queue=hasattr(eng, 'set_piece_queue'), K_local=self.K_local,
+                              n_cu=eng.cu_count(), one_wg=self._one_workgroup_per_cu(),
+                              iter=self.workers[self.k_lo].stan_params['iter'], pieces_per_site=self.PIECES_PER_SITE,
+                              lead_fraction=self.LEAD_FRACTION)
+
+    def _apply_dispatch(self, launch=None, piece=None):
+        """Hand a `dispatch.Launch`, or the piece queue alone, to the engine: the only place `run` sets them."""
+        eng = self.engine
+        if launch is not None:
+            eng.set_site_order(launch.order)
+            eng.set_site_split(launch.n_lead)
+            piece = launch.piece
+        if piece is not None:
+            eng.set_piece_queue(*piece)
 
     def _site_groups(self):
         """Group structure of the sites from `A_k['J']` and `A_n['j_ind']` (the data the
@@ -1217,25 +1236,16 @@ class Master(object):
         per rank.  `self.reuse_log` gets one dict per iteration: `reused, n_ok, khat_max` (the largest smoothed k-hat),
         `wess_min_frac` (the smallest WESS / S), `ms` (the reweighting kernel).  In a reused iteration `stimes` is the
         reweighting's time and `msteps`, `mrhats` keep the values of the last sampled one."""
+        say = print if verbose else (lambda *a, **k: None)
         if niter < 1:
-            if verbose:
-                print("Nothing to do here as provided arg. `niter` is {}".format(niter))
+            say("Nothing to do here as provided arg. `niter` is {}".format(niter))
             return self._ret(self.INFO_OK, calc_moments, return_analytics,
                              (None, None), (None, None, None))
 
         seeds = run_seeds(seed, niter, self.K)                    # :956-960 (per iteration, drawn up front)
         eng = self.engine
-        reuse_on = reuse is not None and reuse is not False
-        if reuse_on:
-            policy = {} if reuse is True else dict(reuse)
-            if set(policy) - {'k_max', 'min_ess'}:
-                raise ValueError("`reuse`: True or a dict with 'k_max' and / or 'min_ess'")
-            if self._sample_injector is not None:
-                raise ValueError('`reuse` needs the draws of the device sampler')
-            eng.set_draw_reuse(True)
-            self.reuse_log = []
-        have_draws = False              # a sampling launch of THIS run left draws and their cavities on the device
-        lo, hi, K = self.k_lo, self.k_hi, self.K
+        reuse = self._reuse_state(reuse)
+        lo, hi = self.k_lo, self.k_hi
         local_workers = self.workers[lo:hi]
 
         # host mirrors -> device (the caller may have edited them between runs)
@@ -1253,93 +1263,24 @@ class Master(object):
         moments = (m_phi_s, cov_phi_s)
         analytics = (stimes, msteps, mrhats, othertimes)
 
+        def leave(info, as_tuple=False):
+            self._download_sites()
+            return self._ret(info, calc_moments, return_analytics, moments, analytics, as_tuple)
+
         for cur_iter in range(niter):
             self.iter += 1
-            if verbose:
-                print("Iter {} starting. Process tilted distributions".format(self.iter))
+            say("Iter {} starting. Process tilted distributions".format(self.iter))
 
             # ---- tilted distributions: ONE batched launch over this rank's sites (:1005-1023)
-            w0 = local_workers[0]
             for w in local_workers:
                 if w.phase != 1:
                     raise RuntimeError('Cavity has to be calculated before tilted.')
             sseeds = stan_seeds(seeds[cur_iter, lo:hi])             # :342-346
-            estim = w0._cur_estim()
-            self._draws_injected = self._sample_injector is not None
-            reused = False
-            if reuse_on:
-                entry = dict(reused=False, n_ok=0, khat_max=float('nan'), wess_min_frac=float('nan'), ms=0.0)
-                if have_draws:
-                    rw_flags, rec, rw_ms = eng.reweight_batch(estim)
-                    khat, wess, S_draws = rec[:, _reweight.RW_KHAT], rec[:, _reweight.RW_WESS], eng.num_draws()
-                    site_ok = _reweight.reuse_ok(khat, wess, S_draws, **policy)
-                    reused = bool(np.all(site_ok))
-                    entry = dict(reused=reused, n_ok=int(np.sum(site_ok)),
-                                 khat_max=float(np.max(np.where(np.isposinf(khat), -np.inf, khat))),
-                                 wess_min_frac=float(np.min(wess)) / S_draws, ms=rw_ms)
-                self.reuse_log.append(entry)
-            if reused:
-                posdefs_l = rw_flags
-                tl = np.full(self.K_local, rw_ms * 1e-3)
-                ml, rl = last_ml, last_rl
-            elif self._sample_injector is not None:
-                posdefs_l, tl, ml, rl = self._tilted_injected(sseeds, estim)
-            else:
-                opts = w0._sampler_opts()
-                if (self.balance_sites and not self.sampling_ms and hasattr(eng, 'set_piece_queue')
-                        and self.K_local > eng.cu_count() and self._one_workgroup_per_cu()):
-                    # no history yet: the piece queue with equal predicted work per transition (the library ignores
-                    # it when the launch does not run the row-wave / state-wave kernel)
-                    eng.set_piece_queue(max(1, w0.stan_params['iter'] // self.PIECES_PER_SITE), None)
-                posdefs_l, stats, ms = eng.tilted_batch(sseeds, opts, estim)
-                for j in np.nonzero(stats[:, 7] > 0)[0]:
-                    posdefs_l[j] = local_workers[j]._void_update()
-                self.last_site_stats = stats        # (K_local, 8): see epx_site_stat in include/epx.h
-                self.sampling_ms.append(ms)
-                self.ngrad_log.append(float(stats[:, 3].sum()))
-                self.pass_log.append(eng.row_passes(w0.stan_params['chains']))
-                # (layout 7: what the row team really did, yielded passes included -- a measurement aid, bench.py)
-                self.team_pass_log.append(float(eng.team_passes().sum()) if eng.last_layout() == 7 else None)
-                if self.balance_sites and self.K_local > 1:
-                    # longest-first dispatch of the next iteration's workgroups (results unaffected)
-                    order, n_lead = self._site_schedule(self.pass_log[-1],
-                                                        eng.get_chain_stats(w0.stan_params['chains'])[:, :, 3],
-                                                        eng.cu_count())
-                    eng.set_site_order(order)
-                    eng.set_site_split(n_lead)
-                    if hasattr(eng, 'set_piece_queue'):
-                        # when a site fills the LDS (one workgroup per CU) and there are more sites than CUs: run the
-                        # sampler from a piece queue -- looping workgroups claim pieces of a site's transitions, the site with
-                        # the largest predicted remaining work first (same draws; only the dispatch changes)
-                        if (eng.last_layout() in (5, 7, 3) and n_lead == 0 and self.K_local > eng.cu_count()
-                                and self._one_workgroup_per_cu()):
-                            it_s = w0.stan_params['iter']
-                            lf = eng.get_chain_stats(w0.stan_params['chains'])[:, :, 3]
-                            eng.set_piece_queue(max(1, it_s // self.PIECES_PER_SITE), np.maximum(lf.max(axis=1), 1.0) / it_s)
-                        else:
-                            eng.set_piece_queue(0)
-                tl = np.full(self.K_local, ms * 1e-3)
-                ml, rl = stats[:, 0], stats[:, 1]
-                last_ml, last_rl = ml, rl
-                have_draws = not np.any(stats[:, 7] > 0)            # (a voided site's draws are its initial points)
-            nsamp = eng.get_tilted(0)[2]
-            for j, w in enumerate(local_workers):
-                w.stan_params['seed'] = int(sseeds[j])
-                w.last_time, w.last_msteps, w.last_mrhat = tl[j], ml[j], rl[j]
-                if w.init_prev:
-                    w.stan_params['init'] = 'prev' if self._sample_injector is None \
-                        else [{}] * w.stan_params['chains']
-                w.nsamp = nsamp
-                if w.prec_estim_skip > 0:
-                    w.prec_estim_skip -= 1
-                w.phase = 2 if posdefs_l[j] else 0
-                if not posdefs_l[j] and w.init_prev:
-                    w.init = w.init_orig                            # sic (:468)
-                w._stale = True
-                w.iteration += 1
-                if save_last_param and cur_iter == niter - 1 and self._sample_injector is None:
-                    w._save_named(save_last_param)
-            n_ok = int(np.sum(posdefs_l))
+            step = self._tilted_step(sseeds, local_workers[0]._cur_estim(), reuse)
+            if reuse is not None:
+                self.reuse_log.append(step.reuse_entry)
+            self._finish_workers(step, sseeds, save_last_param if cur_iter == niter - 1 else None)
+            n_ok = int(np.sum(step.posdefs))
             start_othertime = time.time()
 
             # ---- the one reduction per iteration (:1073-1074, affine in df) and the first damping
@@ -1347,68 +1288,27 @@ class Master(object):
             df = self.df0(self.iter)                                # :1060
             g_pd, c_pd, first_bad, ssum, smax, S, m = self._trial(
                 df, True, stat_sum=(n_ok, self.K_local - n_ok),
-                stat_max=(np.max(tl), np.max(ml), np.max(rl)), want_moments=calc_moments)
-            if verbose:
-                if ssum[1] == 0.0:
-                    print("\rAll sites ok")
-                elif ssum[0] > 0:
-                    print("\rSome sites failed and are not updated")
-                else:
-                    print("\rEvery site failed")
+                stat_max=(np.max(step.times), np.max(step.msteps), np.max(step.mrhats)), want_moments=calc_moments)
+            if ssum[1] == 0.0:
+                say("\rAll sites ok")
+            elif ssum[0] > 0:
+                say("\rSome sites failed and are not updated")
+            else:
+                say("\rEvery site failed")
             if ssum[0] == 0.0:                                      # :1033-1040
-                self._download_sites()
-                return self._ret(self.INFO_ALL_SITES_FAIL, calc_moments, return_analytics,
-                                 moments, analytics)
+                return leave(self.INFO_ALL_SITES_FAIL)
             stimes[cur_iter], msteps[cur_iter], mrhats[cur_iter] = smax[0], smax[1], smax[2]   # :1043-1045
-            if verbose:
-                print("Sampling done, max sampling time {}".format(stimes[cur_iter]))
+            say("Sampling done, max sampling time {}".format(stimes[cur_iter]))
 
             if sweep is not None:                                   # find_damp.py:146-173
                 self.sweep_log.append(self._score_damps(sweep['damps'], sweep['m_target'], sweep['S_target'],
                                                         sweep.get('samp_target')))
                 g_pd, c_pd, first_bad, _, _, S, m = self._trial(df, False, want_moments=calc_moments)
 
-            if verbose:
-                print("Iter {}, starting df {:.3g}".format(self.iter, df))
-            fail_printline = False
-            failed_force_pos_def = False
-            while not (g_pd and c_pd):                              # :1067
-                df *= self.df_decay                                 # :1083 / :1163
-                if verbose:
-                    fail_printline = True
-                    if not g_pd:
-                        sys.stdout.write("\rNon pos. def. posterior cov, " +
-                                         "reducing df to {:.3}".format(df) + " "*5 + "\b"*5)
-                    else:
-                        sys.stdout.write("\rNon pos. def. cavity, " +
-                                         "(first encountered in site {}), ".format(first_bad) +
-                                         "reducing df to {:.3}".format(df) + " "*5 + "\b"*5)
-                    sys.stdout.flush()
-                if not g_pd and self.iter == 1:                     # :1092-1101
-                    if verbose:
-                        print("\nInvalid prior.")
-                    self._download_sites()
-                    return self._ret(self.INFO_INVALID_PRIOR, calc_moments, return_analytics,
-                                     moments, analytics)
-                refresh = False
-                if df < self.df_treshold:                           # :1102-1132 / :1177-1207
-                    if verbose:
-                        print("\nDamping factor reached minimum.")
-                    df = self.df0(self.iter)
-                    if failed_force_pos_def:
-                        if verbose:
-                            print("Failed to force pos_def.")
-                        self._download_sites()
-                        return self._ret(self.INFO_DF_TRESHOLD_REACHED_CAVITY, calc_moments,
-                                         return_analytics, moments, analytics)
-                    failed_force_pos_def = True
-                    forced = eng.force_pd(df, self.MIN_EIG_TRESHOLD, self.MIN_EIG)
-                    if verbose:
-                        print("Force sites {} pos_def.".format(np.nonzero(forced)[0] + lo))
-                    refresh = True                                  # the shift changed Qi: reduce the sums again
-                g_pd, c_pd, first_bad, _, _, S, m = self._trial(df, refresh, want_moments=calc_moments)
-            if verbose and fail_printline:
-                print()
+            accepted = self._damped_update(df, (g_pd, c_pd, first_bad, S, m), calc_moments, verbose)
+            if not isinstance(accepted, tuple):
+                return leave(accepted)
+            df, S, m = accepted
 
             eng.accept(df)                                          # :1145-1158
             self.df_log.append(df)
@@ -1422,22 +1322,59 @@ class Master(object):
                 self.m[...] = m
                 np.copyto(m_phi_s[cur_iter], m)
                 np.copyto(cov_phi_s[cur_iter], S.T)
-                if verbose:
-                    print("Mean and std of phi[0]: {:.3}, {:.3}".format(
-                        m_phi_s[cur_iter, 0], np.sqrt(cov_phi_s[cur_iter, 0, 0])))
+                say("Mean and std of phi[0]: {:.3}, {:.3}".format(
+                    m_phi_s[cur_iter, 0], np.sqrt(cov_phi_s[cur_iter, 0, 0])))
             othertimes[cur_iter] = time.time() - start_othertime   # :1230
             self.othertime_log.append(othertimes[cur_iter])
-            if verbose:
-                print("Iter {} done.".format(self.iter))
+            say("Iter {} done.".format(self.iter))
 
-        self._download_sites()
-        if verbose:
-            print("{} iterations done\nTotal limiting sampling time: {}"
-                  .format(niter, stimes.sum()))
-        return self._ret(self.INFO_OK, calc_moments, return_analytics, moments, analytics,
-                         as_tuple=True)
+        say("{} iterations done\nTotal limiting sampling time: {}"
+            .format(niter, stimes.sum()))
+        return leave(self.INFO_OK, as_tuple=True)
 
-    # ------------------------------------------------------------------
+    # ---- the stages of `run`
+    def _reuse_state(self, reuse):
+        """`run`'s argument `reuse` -> the draw-reuse state of that call (None: off).  The state is the call's own: no
+        draws are carried from one `run` to the next."""
+        if reuse is None or reuse is False:
+            return None
+        policy = {} if reuse is True else dict(reuse)
+        if set(policy) - {'k_max', 'min_ess'}:
+            raise ValueError("`reuse`: True or a dict with 'k_max' and / or 'min_ess'")
+        if self._sample_injector is not None:
+            raise ValueError('`reuse` needs the draws of the device sampler')
+        self.engine.set_draw_reuse(True)
+        self.reuse_log = []
+        return _Reuse(policy)
+
+    def _tilted_step(self, sseeds, estim, reuse):
+        """The tilted moments of this rank's sites, left on the device, from the first source that has them: the
+        reweighted draws of the last launch, the injector (test hook) or a sampling launch.  Returns a `_Tilted`."""
+        self._draws_injected = self._sample_injector is not None
+        entry = None
+        if reuse is not None:
+            entry = dict(reused=False, n_ok=0, khat_max=float('nan'), wess_min_frac=float('nan'), ms=0.0)
+            if reuse.have_draws:
+                step = self._tilted_reweighted(estim, reuse)
+                if step.reuse_entry['reused']:
+                    return step
+                entry = step.reuse_entry
+        if self._sample_injector is not None:
+            return self._tilted_injected(sseeds, estim)
+        return self._tilted_sampled(sseeds, estim, reuse)._replace(reuse_entry=entry)
+
+    def _tilted_reweighted(self, estim, reuse):
+        """The draws of the last sampling launch reweighted to the current cavities.  `reuse_entry['reused']` says
+        whether every local site passed `reweight.reuse_ok`: the moments stand only then."""
+        eng = self.engine
+        flags, rec, ms = eng.reweight_batch(estim)
+        khat, wess, S_draws = rec[:, _reweight.RW_KHAT], rec[:, _reweight.RW_WESS], eng.num_draws()
+        site_ok = _reweight.reuse_ok(khat, wess, S_draws, **reuse.policy)
+        entry = dict(reused=bool(np.all(site_ok)), n_ok=int(np.sum(site_ok)),
+                     khat_max=float(np.max(np.where(np.isposinf(khat), -np.inf, khat))),
+                     wess_min_frac=float(np.min(wess)) / S_draws, ms=ms)
+        return _Tilted(flags, np.full(self.K_local, ms * 1e-3), reuse.msteps, reuse.mrhats, entry)
+
     def _tilted_injected(self, sseeds, estim):
         """Test hook: draws come from `self._sample_injector(data, stan_params)`
         (same role as the reference's `_sample_stan`, method.py:43) and go
@@ -1453,4 +1390,84 @@ class Master(object):
             samples[:, :, j] = samp
         posdefs = eng.moments_batch(samples, estim)
         n = self.K_local
-        return posdefs, np.full(n, 0.25), np.full(n, 0.125), np.full(n, 1.0625)
+        return _Tilted(posdefs, np.full(n, 0.25), np.full(n, 0.125), np.full(n, 1.0625), None)
+
+    def _tilted_sampled(self, sseeds, estim, reuse):
+        """One sampling launch over this rank's sites, its logs, and the dispatch of the next one."""
+        eng = self.engine
+        local_workers = self.workers[self.k_lo:self.k_hi]
+        w0 = local_workers[0]
+        chains = w0.stan_params['chains']
+        rank = self._dispatch_rank()
+        self._apply_dispatch(piece=_dispatch.first_launch(rank, launched=bool(self.sampling_ms)))
+        posdefs, stats, ms = eng.tilted_batch(sseeds, w0._sampler_opts(), estim)
+        voided = np.nonzero(stats[:, 7] > 0)[0]
+        for j in voided:
+            posdefs[j] = local_workers[j]._void_update()
+        self.last_site_stats = stats        # (K_local, 8): see epx_site_stat in include/epx.h
+        self.sampling_ms.append(ms)
+        self.ngrad_log.append(float(stats[:, 3].sum()))
+        self.pass_log.append(eng.row_passes(chains))
+        # (layout 7: what the row team really did, yielded passes included -- a measurement aid, bench.py)
+        self.team_pass_log.append(float(eng.team_passes().sum()) if eng.last_layout() == 7 else None)
+        if _dispatch.schedules(rank):
+            self._apply_dispatch(_dispatch.next_launch(rank, eng.last_layout(), self.pass_log[-1],
+                                                       eng.get_chain_stats(chains)[:, :, 3]))
+        if reuse is not None:
+            reuse.keep(stats[:, 0], stats[:, 1], usable=voided.size == 0)   # (a voided site's draws are its initial points)
+        return _Tilted(posdefs, np.full(self.K_local, ms * 1e-3), stats[:, 0], stats[:, 1], None)
+
+    def _finish_workers(self, step, sseeds, save_param):
+        """What `Worker.tilted` leaves behind on every local worker (method.py:440-475) after a batched tilted step;
+        `save_param`: the names whose draws the workers keep (`run`'s last iteration)."""
+        nsamp = self.engine.get_tilted(0)[2]
+        sampled = self._sample_injector is None
+        for j, w in enumerate(self.workers[self.k_lo:self.k_hi]):
+            w.stan_params['seed'] = int(sseeds[j])
+            w.last_time, w.last_msteps, w.last_mrhat = step.times[j], step.msteps[j], step.mrhats[j]
+            if w.init_prev:
+                w.stan_params['init'] = 'prev' if sampled else [{}] * w.stan_params['chains']
+            w._finish_tilted(step.posdefs[j], nsamp)
+            if save_param and sampled:
+                w._save_named(save_param)
+
+    def _damped_update(self, df0, first_trial, calc_moments, verbose):
+        """From the first trial `(g_pd, c_pd, first_bad, S, m)` at `df0`: decay the damping factor until the global
+        approximation and every cavity are positive definite, below `df_treshold` shift the sites once (`force_pd`)
+        and start over.  Returns the accepted `(df, S, m)`, or the info code that ends the run."""
+        say = print if verbose else (lambda *a, **k: None)
+        df = df0
+        g_pd, c_pd, first_bad, S, m = first_trial
+        say("Iter {}, starting df {:.3g}".format(self.iter, df))
+        fail_printline = False
+        failed_force_pos_def = False
+        while not (g_pd and c_pd):                              # :1067
+            df *= self.df_decay                                 # :1083 / :1163
+            if verbose:
+                fail_printline = True
+                if not g_pd:
+                    sys.stdout.write("\rNon pos. def. posterior cov, " +
+                                     "reducing df to {:.3}".format(df) + " "*5 + "\b"*5)
+                else:
+                    sys.stdout.write("\rNon pos. def. cavity, " +
+                                     "(first encountered in site {}), ".format(first_bad) +
+                                     "reducing df to {:.3}".format(df) + " "*5 + "\b"*5)
+                sys.stdout.flush()
+            if not g_pd and self.iter == 1:                     # :1092-1101
+                say("\nInvalid prior.")
+                return self.INFO_INVALID_PRIOR
+            refresh = False
+            if df < self.df_treshold:                           # :1102-1132 / :1177-1207
+                say("\nDamping factor reached minimum.")
+                df = self.df0(self.iter)
+                if failed_force_pos_def:
+                    say("Failed to force pos_def.")
+                    return self.INFO_DF_TRESHOLD_REACHED_CAVITY
+                failed_force_pos_def = True
+                forced = self.engine.force_pd(df, self.MIN_EIG_TRESHOLD, self.MIN_EIG)
+                say("Force sites {} pos_def.".format(np.nonzero(forced)[0] + self.k_lo))
+                refresh = True                                  # the shift changed Qi: reduce the sums again
+            g_pd, c_pd, first_bad, _, _, S, m = self._trial(df, refresh, want_moments=calc_moments)
+        if fail_printline:
+            print()
+        return df, S, m
