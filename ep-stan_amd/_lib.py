@@ -101,6 +101,12 @@ SIGNATURES = {
                                           ctypes.c_int, c_double_p, c_double_p, ctypes.POINTER(ctypes.c_longlong)]),
     'epx_predict': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int64_p, c_int32_p, c_double_p, c_double_p,
                                    c_double_p, ctypes.c_int, c_double_p, c_int_p]),
+    'epx_predict_new_group': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_longlong,
+                                             ctypes.c_int, ctypes.c_longlong, c_double_p, c_double_p, c_int32_p, ctypes.c_int,
+                                             c_int32_p, c_double_p, ctypes.c_int, c_double_p, c_double_p,
+                                             ctypes.POINTER(ctypes.c_longlong)]),
+    'epx_newgroup_latents': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int32,
+                                            ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, c_double_p]),
     'epx_draw_diagnostics': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int,
                                             ctypes.c_int, c_double_p, c_int_p]),
     'epx_loo': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_int_p]),

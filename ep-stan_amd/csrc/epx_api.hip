@@ -1450,6 +1450,87 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
     return sync.finish();
 }
 
+int epx_predict_new_group(epx_ctx *c, int k0, int count, uint64_t seed, long long t0, int R, long long n, const double *Xn,
+                          const double *yn, const int32_t *row_group, int G, const int32_t *group_label,
+                          const double *theta, int S, double *out, double *out_group, long long *N) {
+    CTX(c);
+    const char *who = "epx_predict_new_group";
+    if (check_range(c, k0, count)) return -1;
+    if (R < 1 || R > EPX_NGP_RMAX) return fail("%s: R must be in 1..%d (got %d)", who, (int)EPX_NGP_RMAX, R);
+    if (c->D > EPX_PR_DMAX) return fail("%s: D = %d columns, at most %d", who, c->D, (int)EPX_PR_DMAX);
+    if (n < 0 || n > 0x7fffffff) return fail("%s: %lld rows in one call, between 0 and 2^31 - 1", who, n);
+    if (G < 0 || (G > 0 && !group_label)) return fail("%s: G = %d groups need their labels", who, G);
+    if (t0 < 0 || t0 > (1ll << 32)) return fail("%s: t0 = %lld outside [0,2^32]", who, t0);
+    if (n > 0 && (!Xn || !out)) return fail("%s: Xn and out are required", who);
+    for (int g = 0; g < G; ++g)
+        if (group_label[g] < 0) return fail("%s: group %d: label %d is negative", who, g, (int)group_label[g]);
+    // rows sorted by group, stable: perm[sorted position] = row
+    std::vector<int> gfirst((size_t)G + 1, 0), perm((size_t)n), live;
+    for (long long i = 0; i < n; ++i) {
+        const int g = row_group ? row_group[i] : 0;
+        if (g < 0 || g >= G) return fail("%s: row %lld: group %d outside [0,%d)", who, i, g, G);
+        ++gfirst[(size_t)g + 1];
+    }
+    if (yn)
+        for (long long i = 0; i < n; ++i) {
+            if (c->gauss ? !std::isfinite(yn[i]) : (yn[i] != 0.0 && yn[i] != 1.0))
+                return fail("%s: row %lld: y = %g, %s", who, i, yn[i],
+                            c->gauss ? "the Gaussian models take finite responses" : "the Bernoulli models take 0 or 1");
+        }
+    for (int g = 0; g < G; ++g) {
+        if (gfirst[(size_t)g + 1] > 0) live.push_back(g);
+        gfirst[(size_t)g + 1] += gfirst[g];
+    }
+    {
+        std::vector<int> at(gfirst.begin(), gfirst.end() - 1);
+        for (long long i = 0; i < n; ++i) perm[(size_t)at[row_group ? row_group[i] : 0]++] = (int)i;
+    }
+    NewGroupArgs a;
+    DrawSource src;
+    if (draw_source(c, who, k0, count, theta, S, nullptr, &src)) return -1;
+    const long long T = (long long)count * src.S;
+    if (t0 + T > (1ll << 32))
+        return fail("%s: pooled draws [%lld,%lld) outside [0,2^32)", who, t0, t0 + T);
+    a.N = T * R;
+    if (N) *N = a.N;
+    if (n == 0) return 0;
+    a.model = c->model; a.D = c->D; a.d = c->d; a.gauss = c->gauss; a.P = c->P;
+    a.KP = (1 + c->D + 3) / 4 * 4;
+    a.E = c->model == EPX_M1B_SG ? 1 : 1 + c->D; a.lap = c->model == EPX_M5B_SG;
+    a.R = R; a.t0 = t0; a.seed = seed; a.n = (int)n; a.G = G;
+    a.chunk_slabs = newgroup_chunk_slabs(a.N);
+    const long long chunk = (long long)a.chunk_slabs * 16;
+    a.nchunk = (a.N + chunk - 1) / chunk;
+    a.nitem = (long long)live.size() * a.nchunk;
+    const size_t nn = (size_t)n, D = c->D, nG = (size_t)G, nch = (size_t)a.nchunk;
+    HIPCHK(c->pred_ws.grow(nn * D + nn + nch * nn * EPX_PR_COUNT + nch * nG + nn * EPX_PR_COUNT + nG * EPX_NG_COUNT));
+    HIPCHK(c->pred_iws.grow(nn + (nG + 1) + nG + live.size()));
+    double *X_d = c->pred_ws, *y_d = X_d + nn * D, *rows_d = y_d + nn, *grp_d = rows_d + nch * nn * EPX_PR_COUNT;
+    double *out_d = grp_d + nch * nG, *outg_d = out_d + nn * EPX_PR_COUNT;
+    int *perm_d = c->pred_iws, *gfirst_d = perm_d + nn, *label_d = gfirst_d + nG + 1, *live_d = label_d + nG;
+    StreamSync sync{c->stream};          // (`perm`, `gfirst` and `live` are this frame's: the guard is declared behind them)
+    if (upload_draws(c, src, &a.draws)) return -1;
+    HIPCHK(hipMemcpyAsync(X_d, Xn, nn * D * 8, hipMemcpyHostToDevice, c->stream));
+    if (yn) HIPCHK(hipMemcpyAsync(y_d, yn, nn * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(perm_d, perm.data(), nn * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(gfirst_d, gfirst.data(), (nG + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(label_d, group_label, nG * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(live_d, live.data(), live.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    a.perm = perm_d; a.gfirst = gfirst_d; a.label = label_d; a.live = live_d;
+    a.X = X_d; a.y = yn ? y_d : nullptr;
+    a.part_rows = rows_d; a.part_grp = grp_d; a.out = out_d; a.out_group = outg_d;
+    // the grid: every item its own workgroup up to a few per compute unit, then they walk
+    const long long grid_cap = (long long)(c->n_cu > 0 ? c->n_cu : 256) * 4;
+    hipLaunchKernelGGL(k_newgroup, dim3((unsigned)(a.nitem < grid_cap ? a.nitem : grid_cap)), dim3(256), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    const long long mblocks = ((long long)n + G + 255) / 256;
+    hipLaunchKernelGGL(k_newgroup_merge, dim3((unsigned)(mblocks < 65536 ? mblocks : 65536)), dim3(256), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, out_d, nn * EPX_PR_COUNT * 8, hipMemcpyDeviceToHost, c->stream));
+    if (out_group) HIPCHK(hipMemcpyAsync(out_group, outg_d, nG * EPX_NG_COUNT * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync.finish();
+}
+
 // LDS of the per-row PSIS stage (psis.h): 16 rows' scratch
 static size_t psis_lds_bytes(int M) { return (size_t)16 * psis_scratch_doubles(M) * 8; }
 
@@ -1818,6 +1899,32 @@ int epx_psis_rows(int device, long long n, int S, const double *ll, double *out)
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, outd, (size_t)n * 3 * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int epx_newgroup_latents(int device, int model, int D, uint64_t seed, int32_t label, long long t0, long long nt, int R,
+                         double *out) {
+    DeviceGuard guard;
+    if (need_device(device)) return -1;
+    const char *who = "epx_newgroup_latents";
+    if (model < EPX_M1B_SG || model > EPX_M5A_SG) return fail("%s: unknown model %d", who, model);
+    if (D < 1 || D > EPX_PR_DMAX) return fail("%s: D = %d columns, between 1 and %d", who, D, (int)EPX_PR_DMAX);
+    if (label < 0) return fail("%s: label %d is negative", who, (int)label);
+    if (R < 1 || R > EPX_NGP_RMAX) return fail("%s: R must be in 1..%d (got %d)", who, (int)EPX_NGP_RMAX, R);
+    if (t0 < 0 || nt < 0 || t0 > (1ll << 32) || nt > (1ll << 32) || t0 + nt > (1ll << 32))
+        return fail("%s: pooled draws [%lld,%lld) outside [0,2^32)", who, t0, t0 + nt);
+    if (nt == 0) return 0;
+    if (!out) return fail("%s: out is required", who);
+    const int b = model % 5, E = b == EPX_M1B_SG ? 1 : 1 + D;
+    const size_t total = (size_t)nt * R * E;
+    DevBuf<double> od;
+    HIPCHK(od.alloc(total));
+    const long long blocks = (nt * R * ((E + 1) / 2) + 255) / 256;
+    hipLaunchKernelGGL(k_newgroup_latents, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, 0, seed,
+                       (int)label, t0, nt, R, E, b == EPX_M5B_SG ? 1 : 0, od);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, od, total * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -193,6 +193,40 @@ struct PredictArgs {
 };
 __global__ void k_predict(PredictArgs a);
 
+// Posterior predictive of a group that was not in the data (newgroup.inc; include/epx.h: epx_predict_new_group).  The
+// pool of N = count x S x R members is cut into chunks of whole slabs of 16 members; a work item of k_newgroup is
+// (new group with rows, chunk), a workgroup walks its items.
+enum { EPX_NGP_MIN_SLABS = 16, EPX_NGP_MAX_SLABS = 128, EPX_NGP_CHUNKS = 256, EPX_NGP_RMAX = 1024 };
+// slabs per chunk: a function of N alone -- about EPX_NGP_CHUNKS chunks, of 16 to 128 slabs (what gll of k_newgroup holds)
+constexpr int newgroup_chunk_slabs(long long N) {
+    const long long nslab = (N + 15) / 16, want = (nslab + EPX_NGP_CHUNKS - 1) / EPX_NGP_CHUNKS;
+    return (int)(want < EPX_NGP_MIN_SLABS ? EPX_NGP_MIN_SLABS : want > EPX_NGP_MAX_SLABS ? EPX_NGP_MAX_SLABS : want);
+}
+struct NewGroupArgs {
+    int model, D, d, gauss, P;
+    int KP;                            // 1 + D rounded up to a multiple of 4 (PredictArgs)
+    int E, lap;                        // latents per member: 1 (m1) or 1 + D; m5: Laplace instead of normal
+    int R, chunk_slabs;
+    long long N, t0;                   // pool members; pooled index of the first draw of the call
+    long long nchunk, nitem;           // chunks of the pool; work items = groups with rows x nchunk
+    uint64_t seed;
+    int n, G;                          // rows, new groups
+    const double *draws;               // (count x S, P) row-major: draw bs at draws + bs * P, phi = its first d
+    const int *perm;                   // sorted (by group, stable) position -> row of the caller
+    const int *gfirst;                 // G + 1: first sorted position of every group
+    const int *label;                  // G: the stream's label of every group
+    const int *live;                   // the groups with rows, ascending
+    const double *X;                   // n x D row-major, the caller's order
+    const double *y;                   // n, or NULL: no LPD, no GLPD
+    double *part_rows;                 // nchunk x n (sorted positions) x EPX_PR_COUNT: the chunks' records
+    double *part_grp;                  // nchunk x G: the chunks' joint terms
+    double *out;                       // n x EPX_PR_COUNT, the caller's order
+    double *out_group;                 // G x EPX_NG_COUNT
+};
+__global__ void k_newgroup(NewGroupArgs a);
+__global__ void k_newgroup_merge(NewGroupArgs a);
+__global__ void k_newgroup_latents(uint64_t seed, int label, long long t0, long long nt, int R, int E, int lap, double *out);
+
 // Leave-one-out cross-validation of the context's own rows (predict.hip: k_loo; include/epx.h: epx_loo) and the per-row
 // PSIS stage alone (k_psis_rows; epx_psis_rows); psis.h holds the per-row code and the sizes of its scratch.
 struct LooArgs {
@@ -257,7 +291,8 @@ __global__ void k_force_pd(ForceArgs a);
 // ------------------------------------------------------------------ sampler
 enum { ST_STEPSIZE_MEAN = 0, ST_STEPSIZE_FINAL, ST_NLEAP, ST_NGRAD, ST_NDIV, ST_ACCEPT_MEAN,
        ST_DEPTH_MEAN, ST_FAIL, ST_COUNT };
-enum { K_INIT = 0, K_MOM = 1, K_DIR = 2, K_TOP = 3, K_MERGE = 4, K_SSMOM = 5 };
+enum { K_INIT = 0, K_MOM = 1, K_DIR = 2, K_TOP = 3, K_MERGE = 4, K_SSMOM = 5,
+       K_NEWGROUP = 6 };   // the latents of a new group (newgroup.inc): disjoint from every sampler stream
 enum { MAX_DEPTH_CAP = 12 };
 // seconds a workgroup of a pieced launch looks for a site before it reports a lost piece (epx_pieces.h); the environment
 // variable of the same name overrides it at run time (NutsArgs::dyn_wait_s)

@@ -179,6 +179,8 @@ k_predict(PredictArgs a) {
     }
 }
 
+#include "newgroup.inc"              // k_newgroup, k_newgroup_merge, k_newgroup_latents: a group that was not in the data
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Leave-one-out cross-validation of the context's OWN rows (include/epx.h, enum epx_loo; loo.loo_host is the NumPy
 // statement).  A workgroup takes work items of up to `tiles` x 16 rows of ONE (site, group), in the context's row order

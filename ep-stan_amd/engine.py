@@ -543,6 +543,48 @@ class HipEngine(object):
                                    dptr(Xn), dptr(y), dptr(theta), int(S), dptr(out), None))
         return out
 
+    def predict_new_group(self, Xn, gidx, labels, y=None, seed=0, t0=0, R=1, k0=0, count=None, theta=None):
+        """Posterior predictive of groups that were not in the data (epx_predict_new_group, include/epx.h):
+        (rows (n, 4), glpd (G,), N) -- the columns of `predict` over the pool of N = count S R members, and the joint
+        log predictive density of every new group's responses (NaN without y).  Xn (n, D); gidx (n): dense index of
+        the row's new group (None: 0); labels (G): the stream's label of every group; t0: pooled index of site k0's
+        first draw.  The draws are those of the last sampling call, on the device; `theta` (count, S, P) injects
+        draws instead (test hook)."""
+        count = self.K - k0 if count is None else count
+        Xn = np.ascontiguousarray(Xn, dtype=np.float64)
+        if Xn.ndim != 2 or Xn.shape[1] != self.D:
+            raise ValueError('Xn: (n, D) = (n, {})'.format(self.D))
+        n = Xn.shape[0]
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if gidx is not None:
+            gidx = np.ascontiguousarray(gidx, dtype=np.int32)
+            if gidx.shape != (n,):
+                raise ValueError('gidx: one group per new row')
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.float64)
+            if y.shape != (n,):
+                raise ValueError('y: one response per new row')
+        theta, S = self._injected(theta, count)
+        G = labels.shape[0]
+        out = np.zeros((n, _site_params.PR_COUNT))
+        glpd = np.zeros(G)
+        N = ctypes.c_longlong()
+        check(self.lib.epx_predict_new_group(
+            self.ctx, int(k0), int(count), ctypes.c_uint64(int(seed)), int(t0), int(R), n, dptr(Xn), dptr(y),
+            gidx.ctypes.data_as(_lib.c_int32_p) if gidx is not None else None, G, labels.ctypes.data_as(_lib.c_int32_p),
+            dptr(theta), int(S), dptr(out), dptr(glpd), ctypes.byref(N)))
+        if n == 0:                                       # nothing launched: groups without rows
+            glpd[:] = np.nan if y is None else 0.0
+        return out, glpd, N.value
+
+    def newgroup_latents(self, seed, label, t0, nt, R):
+        """TEST HOOK: the latents (nt, R, E) of new group `label` at the pooled draws t0..t0+nt (epx_newgroup_latents)."""
+        E = 1 if MODEL_IDS[self.model] % 5 == 0 else 1 + self.D
+        out = np.zeros((max(int(nt), 0), max(int(R), 0), E))
+        check(self.lib.epx_newgroup_latents(int(self.device), MODEL_IDS[self.model], self.D, ctypes.c_uint64(int(seed)),
+                                            int(label), int(t0), int(nt), int(R), dptr(out)))
+        return out
+
     def loo(self, k0=0, count=None, theta=None, with_n=False):
         """Leave-one-out records of the context's own rows of the sites k0..k0+count (epx_loo, include/epx.h):
         (rows, 6), columns loo.LO_LPD, LO_LL_MEAN, LO_LL_M2, LO_ELPD, LO_KHAT, LO_WESS, in the context's row order.  The

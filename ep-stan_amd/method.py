@@ -36,6 +36,7 @@ from . import dist as _dist
 from . import engine as _engine
 from . import loo as _loo
 from . import mix_pred as _mix_pred
+from . import newgroup as _newgroup
 from . import quantiles as _quantiles
 from . import reweight as _reweight
 from . import site_params as _site_params
@@ -1022,6 +1023,85 @@ class Master(object):
         return dict(mean=out[:, _site_params.PR_MEAN].copy(), f_mean=out[:, _site_params.PR_F_MEAN].copy(),
                     f_var=out[:, _site_params.PR_F_M2] / (S - 1),
                     lpd=out[:, _site_params.PR_LPD].copy() if ys is not None else None, n=S)
+
+    def _local_predict_new_group(self, Xn, gidx, labels, y, seed, R):
+        """(rows (n, 4), glpd (G,), N) of new groups against this rank's sites' draws (see HipEngine.predict_new_group).
+        The device engine computes them next to the draws; an engine without `predict_new_group` (the CPU oracle the
+        tests inject) hands the phi of its draws to newgroup.predict_new_group_host."""
+        eng = self.engine
+        t0 = self.k_lo * eng.num_draws()
+        if hasattr(eng, 'predict_new_group'):
+            return eng.predict_new_group(Xn, gidx, labels, y, seed=seed, t0=t0, R=R)
+        mid, gauss, _ = self._site_spec()
+        phi = np.stack([np.ascontiguousarray(eng.get_draws(j)) for j in range(self.K_local)])
+        return _newgroup.predict_new_group_host(mid, self.D, gauss, phi, Xn, gidx, labels, y, seed, t0, R)
+
+    def predict_new_group(self, X_new, group=None, y_new=None, R=1, seed=0):
+        """Posterior predictive of rows of groups that were NOT in the data, from the tilted draws of the last iteration
+        (the reference has no counterpart; include/epx.h, epx_predict_new_group, states the definition).  The new
+        group's own eta, etb are drawn from the model's prior -- normal(0, 1), double_exponential(0, 1) for m5 -- by a
+        counter-based stream, `R` independent replicates per draw, and the pool of ALL sites' phi draws is pushed
+        through them: N = K x draws per site x R pool members.
+
+        X_new (n, D); group: an integer label in [0, 2^31) per row (None: one group, label 0) -- rows with the same
+        label share the latents, and a label names its stream: the same (seed, label) gives the same latents whatever
+        else is in the call; y_new: responses of the new rows, for the log predictive densities; seed: of the stream.
+
+        Returns a dict: `mean`, `f_mean`, `f_var`, `lpd` (n) as `predict` returns them, over the N pool members (lpd is
+        None without `y_new`); `groups` the sorted distinct labels and `group_lpd` the joint log predictive density of
+        each one's responses, log mean_n exp(sum_i ll_ni) over its rows (None without `y_new`) -- the rows of a group
+        share the member's latents, so this is NOT the sum of their `lpd`; `n` = N.  Rows in the caller's order.  With
+        several ranks every rank runs all rows against its own sites' draws, and one collective of a rank-slotted
+        record followed by newgroup.merge in rank order makes every rank return the same result."""
+        self._need_draws("predict a new group", "nothing can be predicted from them")
+        X_new = np.asarray(X_new, dtype=np.float64)
+        if X_new.ndim != 2 or X_new.shape[1] != self.D:
+            raise ValueError("Argument `X_new` should be two dimensional with {} columns".format(self.D))
+        n = X_new.shape[0]
+        if group is None:
+            group = np.zeros(n, dtype=np.int64)
+        group = np.asarray(group)
+        if group.shape != (n,) or not np.issubdtype(group.dtype, np.integer):
+            raise ValueError("`group`: one integer label per row of `X_new`")
+        bad = np.nonzero((group < 0) | (group >= 2 ** 31))[0]
+        if bad.size:
+            raise ValueError("`group` of row {}: label {} outside [0, 2^31)".format(int(bad[0]), int(group[bad[0]])))
+        if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 1 <= R <= _newgroup.R_MAX:
+            raise ValueError("`R`: an integer number of replicates in 1..{}".format(_newgroup.R_MAX))
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+            raise ValueError("`seed`: an integer in [0, 2^64)")
+        mid, gauss, _ = self._site_spec()
+        ys = None
+        if y_new is not None:
+            ys = np.ascontiguousarray(y_new, dtype=np.float64)
+            if ys.shape != (n,):
+                raise ValueError("The shapes of `y_new` and `X_new` does not match")
+            bad = np.nonzero(~np.isfinite(ys) if gauss else (ys != 0) & (ys != 1))[0]
+            if bad.size:
+                raise ValueError("`y_new` of row {}: {}; site model {!r} takes {}".format(
+                    int(bad[0]), ys[bad[0]], self.model_name, "finite responses" if gauss else "responses 0 or 1"))
+        S = self.engine.num_draws()
+        if self.K * S > 2 ** 32:
+            raise ValueError("{} sites x {} draws: more than 2^32 pooled draws".format(self.K, S))
+        labels, gidx = np.unique(group, return_inverse=True)
+        G = labels.shape[0]
+        rows, glpd, N = self._local_predict_new_group(np.ascontiguousarray(X_new), gidx.astype(np.int32), labels, ys,
+                                                      int(seed), int(R))
+        world = self.comm.world
+        if world > 1:
+            # every rank's record in its own slot, one sum, the pools merged in rank order
+            width = n * _site_params.PR_COUNT + G + 1
+            rec = np.zeros((world, width))
+            mine = np.concatenate((rows.reshape(-1), glpd, [float(N)]))
+            rec[self.comm.rank] = np.where(np.isnan(mine), 0.0, mine) if ys is None else mine
+            rec = np.asarray(self.comm.allreduce_sum(rec.reshape(-1))).reshape(world, width)
+            parts = [(rec[r, :n * _site_params.PR_COUNT].reshape(n, _site_params.PR_COUNT),
+                      rec[r, n * _site_params.PR_COUNT:-1], int(round(rec[r, -1]))) for r in range(world)]
+            rows, glpd, N = _newgroup.merge(parts)
+        return dict(mean=rows[:, _site_params.PR_MEAN].copy(), f_mean=rows[:, _site_params.PR_F_MEAN].copy(),
+                    f_var=rows[:, _site_params.PR_F_M2] / (N - 1),
+                    lpd=rows[:, _site_params.PR_LPD].copy() if ys is not None else None,
+                    groups=labels.astype(np.int64), group_lpd=np.array(glpd) if ys is not None else None, n=N)
 
     def _local_loo(self):
         """Leave-one-out records (rows of this rank's sites, 6) and the draws per site (see HipEngine.loo).  The device

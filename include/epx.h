@@ -346,6 +346,54 @@ enum epx_pred { EPX_PR_MEAN = 0, EPX_PR_F_MEAN, EPX_PR_F_M2, EPX_PR_LPD, EPX_PR_
 int epx_predict(epx_ctx *ctx, int k0, int count, const int64_t *row_lim, const int32_t *row_group, const double *Xn,
                 const double *yn, const double *theta, int S, double *out, int *nsamp);
 
+/* Posterior predictive of a group that was NOT in the data (no counterpart in the reference): the new group's own latents
+ * are drawn from the model's prior on the device and the pool of all sites' phi draws is pushed through them.  The
+ * definition, stated once; the kernels (csrc/newgroup.inc) and newgroup.predict_new_group_host both follow it.
+ * Pool.  The sites k0..k0+count hold S draws each; only the first d = dphi coordinates phi of a draw record are read
+ *   (record stride P: multi-group contexts are fine).  Every draw is used with R >= 1 independent replicates of the new
+ *   group's latents: a pool member is (b, s, r), b < count, s < S, r < R, N = count S R of them.  The pooled draw index is
+ *   t = t0 + b S + s, t0 being the index of site k0's first draw among ALL sites of ALL ranks (Master passes
+ *   (k_lo + k0) S: results do not depend on how the sites are sharded); t0 + count S <= 2^32.
+ * Latents of new group `label` (0 <= label < 2^31) at (t, r): E = 1 + D elements for the models with an etb block
+ *   (m2..m5), E = 1 for m1; element e = 0 is eta, e = 1 + j is etb_j.  With (u1, u2) the two uniforms of the samplers'
+ *   Philox4x32-10 stream at key (seed, chain = label) and counter (t, kind 6 = K_NEWGROUP, e >> 1, r) -- a kind no sampler
+ *   uses -- m1..m4 (eta, etb ~ normal(0, 1)) take the Box-Muller pair shared by e and e ^ 1,
+ *   z_e = sqrt(-2 log u1) cos(2 pi u2) for even e, ... sin ... for odd e; m5 (double_exponential(0, 1)) takes u = u2 for
+ *   odd e, else u1, x = u - 1/2, z_e = -sign(x) log1p(-2 |x|).  u lies in the open interval: z_e is finite.  A latent
+ *   depends on (seed, label, t, r, e) only.
+ * Coefficients.  alpha_n, beta_n as EPX_NM_ALPHA / EPX_NM_BETA form them, with eta := z_0, etb_j := z_{1+j} (m1 takes
+ *   beta from phi); f_{n,i} = alpha_n + x_i . beta_n; link and ll_{n,i} as in EPX_PR_LPD above.
+ * Per row i, over the N pool members: the four columns of enum epx_pred with S read as N (F_M2 centred, LPD a
+ *   log-mean-exp about the largest term, NaN when yn == NULL).
+ * Per new group g with rows I_g: EPX_NG_GLPD = log (1/N) sum_n exp(sum_{i in I_g} ll_{n,i}), the joint log predictive
+ *   density of the group's responses -- all rows of the group share the member's latents; a log-mean-exp about the
+ *   largest sum, finite where every term underflows; 0 for a group without rows; NaN when yn == NULL.
+ * Merging two disjoint pools a, b (chunks of the pool inside the call; ranks, on the host: newgroup.merge):
+ *   the means by weights; M2 = M2_a + M2_b + (fmean_a - fmean_b)^2 N_a N_b / N;
+ *   lpd = logaddexp(lpd_a + log N_a, lpd_b + log N_b) - log N, taken about the larger term; GLPD like lpd.
+ * Results, never faults: log sigma = -800 gives exp = 0 and the latents drop out; non-finite phi gives what the
+ * arithmetic gives, for the rows and groups it touches only.
+ * Xn (n x D row-major), yn (n; 0 or 1 for the Bernoulli models, finite for the Gaussian ones; or NULL), row_group (n:
+ * dense index 0..G-1 of the row's new group, any order; NULL: all 0), group_label (G), out (n x EPX_PR_COUNT) and out_group
+ * (G x EPX_NG_COUNT, may be NULL) are host arrays; N out (may be NULL): the pool's members.  n == 0 returns N without a
+ * launch and writes neither out nor out_group.  theta == NULL: the draws of the last sampling call (error "no draws yet"
+ * before one, and an error when that call did not cover every site of the range), S is ignored; otherwise TEST HOOK:
+ * injected draws (count, S, P) row-major.  1 <= R <= 1024, at most D = 128 columns.  The pool is cut into chunks of whole
+ * slabs of 16 members by a rule that depends on N alone; chunk records go to a workspace of the context and are merged in
+ * ascending order.  No floating-point atomics: the same bits on every call, and the bits of a row's record or of a
+ * group's GLPD do not depend on which other rows or groups are in the call.  Stream-ordered, one synchronisation. */
+enum epx_newgroup { EPX_NG_GLPD = 0, EPX_NG_COUNT };
+int epx_predict_new_group(epx_ctx *ctx, int k0, int count, uint64_t seed, long long t0, int R,
+                          long long n, const double *Xn /* n x D */, const double *yn /* n or NULL */,
+                          const int32_t *row_group /* n, dense 0..G-1, or NULL: all 0 */,
+                          int G, const int32_t *group_label /* G: the stream's label of each group */,
+                          const double *theta, int S,          /* NULL: last sampling call; else TEST HOOK (count,S,P) */
+                          double *out /* n x EPX_PR_COUNT */, double *out_group /* G x EPX_NG_COUNT, may be NULL */,
+                          long long *N);
+/* TEST HOOK, no context: latents of `label` at pooled draws t0..t0+nt, replicates 0..R: out (nt, R, E) */
+int epx_newgroup_latents(int device, int model, int D, uint64_t seed, int32_t label, long long t0,
+                         long long nt, int R, double *out);
+
 /* Leave-one-out cross-validation of the context's OWN rows from the draws of the sites k0..k0+count: PSIS-LOO (Pareto-
  * smoothed importance sampling) with its Pareto k-hat diagnostic, and what WAIC needs (no counterpart in the reference).
  * The definition, stated once; the kernels k_loo / k_psis_rows (csrc/predict.hip, csrc/psis.h) and loo.psis_host /
