@@ -109,6 +109,10 @@ SIGNATURES = {
                                             ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, c_double_p]),
     'epx_draw_diagnostics': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int,
                                             ctypes.c_int, c_double_p, c_int_p]),
+    'epx_draw_rank_diagnostics': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int,
+                                                 ctypes.c_int, c_double_p, c_int_p]),
+    'epx_rank_normalize': (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_int, c_double_p, ctypes.c_int,
+                                          c_double_p, c_double_p]),
     'epx_loo': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_int_p]),
     'epx_psis_rows': (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_int, c_double_p, c_double_p]),
     'epx_damp_sweep': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, ctypes.c_void_p,

@@ -21,6 +21,7 @@
 // order, nothing is merged across workgroups, no atomics: the same bits on every call.  The z phase stages its tile in
 // the same LDS; its draws come from L2.
 #include "epx_kernels.h"
+#include "geyer.h"
 
 namespace epx {
 
@@ -128,32 +129,12 @@ __device__ inline DiagPhase diag_phase(const DiagArgs &a, const double *X, bool 
                 for (int q = 0; q < DG_NS; ++q) s += part[(q * DG_LB + j) * DG_TW + c];
                 rho[j] = s / ((double)h * (double)M);      // mean over the half chains of acov_m(t0 + j)
             }
-            if (t0 == 0) {
-                r.W = rho[0] * (double)h / (double)(h - 1);
-                r.var_plus = r.W * (double)(h - 1) / (double)h + between;
-                if (!(r.W > 0.0) || !isfinite(r.W)) done = 1;        // constant, or a non-finite draw
-            }
-#pragma unroll
-            for (int j = 0; j < DG_LB; ++j) rho[j] = 1.0 - (r.W - rho[j]) / r.var_plus;
-#pragma unroll
-            for (int j = 0; j < DG_LB; j += 2) {
-                if (done) break;
-                const int t = t0 + j;
-                if (t + 1 >= h) { done = 1; break; }
-                double p = (t == 0 ? 1.0 : rho[j]) + rho[j + 1];
-                if (!(p > 0.0)) { done = 1; break; }
-                p = p < prev ? p : prev;
-                prev = p;
-                pairs += p;
-            }
+            geyer_block(rho, t0, h, between, r.W, r.var_plus, prev, pairs, done);
             done_s[c] = done;
         }
         if (!__syncthreads_or(slot == 0 && !done)) break;
     }
-    if (slot == 0 && r.W > 0.0 && isfinite(r.W)) {
-        const double tau = -1.0 + 2.0 * pairs;
-        r.ess = (double)((long long)M * h) / (tau > a.tau_min ? tau : a.tau_min);
-    }
+    if (slot == 0 && r.W > 0.0 && isfinite(r.W)) r.ess = geyer_ess((long long)M * h, pairs, a.tau_min);
     return r;
 }
 

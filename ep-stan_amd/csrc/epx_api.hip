@@ -1630,6 +1630,41 @@ int epx_draw_diagnostics(epx_ctx *c, int k0, int count, const double *theta, int
     return sync.finish();
 }
 
+int epx_draw_rank_diagnostics(epx_ctx *c, int k0, int count, const double *theta, int S, int chains, double *out,
+                              int *nsamp) {
+    CTX(c);
+    if (check_range(c, k0, count)) return -1;
+    if (!out) return fail("epx_draw_rank_diagnostics: out is required");
+    const size_t P = c->P;
+    RankDiagArgs a;
+    DrawSource src;
+    if (draw_source(c, "epx_draw_rank_diagnostics", k0, count, theta, S, &chains, &src)) return -1;
+    S = src.S; chains = src.chains;
+    if (chains > EPX_DG_MAX_CHAINS)
+        return fail("epx_draw_rank_diagnostics: %d chains, at most %d", chains, (int)EPX_DG_MAX_CHAINS);
+    a.k0 = k0; a.chains = chains; a.nkeep = S / chains; a.P = c->P;
+    a.d = c->d; a.pg = c->pg; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    const long long n = 2ll * chains * (a.nkeep / 2);
+    if (n > EPX_RD_MAX_DRAWS)
+        return fail("epx_draw_rank_diagnostics: %lld used draws per site, at most %d (a coordinate's keys, draw indices and "
+                    "scores are kept in LDS)", n, (int)EPX_RD_MAX_DRAWS);
+    if ((size_t)count * P > 0x7fffffffull)
+        return fail("epx_draw_rank_diagnostics: %d sites x %zu coordinates in one call, at most 2^31 - 1", count, P);
+    a.tau_min = n > 1 ? 1.0 / log10((double)n) : 0.0;
+    const size_t lds = rank_lds_bytes((int)n);
+    if (set_lds(k_rank_diag, lds)) return -1;
+    StreamSync sync{c->stream};
+    if (upload_draws(c, src, &a.draws)) return -1;
+    const size_t nout = (size_t)count * P * EPX_RD_COUNT;
+    HIPCHK(c->rank_out.grow(nout));
+    a.out = c->rank_out;
+    hipLaunchKernelGGL(k_rank_diag, dim3((unsigned)((size_t)count * P)), dim3(EPX_RD_THREADS), lds, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, a.out, nout * 8, hipMemcpyDeviceToHost, c->stream));
+    if (nsamp) *nsamp = (int)n;
+    return sync.finish();
+}
+
 int epx_pooled_moments(epx_ctx *c, int k0, int count, const double *center, const double *theta, int S, int want_scatter,
                        double *sum, double *scatter, long long *n) {
     CTX(c);
@@ -1899,6 +1934,33 @@ int epx_psis_rows(int device, long long n, int S, const double *ll, double *out)
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, outd, (size_t)n * 3 * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int epx_rank_normalize(int device, long long m, int n, const double *x, int fold, double *rank_out, double *z_out) {
+    DeviceGuard guard;
+    if (need_device(device)) return -1;
+    if (m < 0 || m > 0x7fffffffll || n < 1) return fail("epx_rank_normalize: m = %lld series of n = %d values", m, n);
+    if (n > EPX_RD_MAX_DRAWS)
+        return fail("epx_rank_normalize: n = %d values per series, at most %d (a series' keys, indices and scores are kept "
+                    "in LDS)", n, (int)EPX_RD_MAX_DRAWS);
+    if (m == 0) return 0;
+    if (!x || !rank_out || !z_out) return fail("epx_rank_normalize: x, rank_out and z_out are required");
+    RankNormArgs a;
+    a.n = n; a.fold = fold ? 1 : 0;
+    const size_t total = (size_t)m * n, lds = rank_lds_bytes(n);
+    DevBuf<double> xd, rd, zd;
+    HIPCHK(xd.alloc(total));
+    HIPCHK(rd.alloc(total));
+    HIPCHK(zd.alloc(total));
+    HIPCHK(hipMemcpy(xd, x, total * 8, hipMemcpyHostToDevice));
+    a.x = xd; a.rank = rd; a.z = zd;
+    if (set_lds(k_rank_normalize, lds)) return -1;
+    hipLaunchKernelGGL(k_rank_normalize, dim3((unsigned)m), dim3(EPX_RD_THREADS), lds, 0, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(rank_out, rd, total * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(z_out, zd, total * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

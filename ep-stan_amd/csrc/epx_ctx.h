@@ -128,6 +128,7 @@ struct epx_ctx {
     DevBuf<int> pred_iws;           // ... [workgroup records (4 ints each) | sorted position -> row (n)]
     DevBuf<double> loo_ws;          // epx_loo: [results (rows x EPX_LO_COUNT) | log-likelihood slabs, one per workgroup, when LDS is too small]
     DevBuf<double> diag_out;        // epx_draw_diagnostics: the call's records (count x P x EPX_DG_COUNT)
+    DevBuf<double> rank_out;        // epx_draw_rank_diagnostics: the call's records (count x P x EPX_RD_COUNT)
     DevBuf<double> order_out;       // epx_named_order_stats: the call's order statistics (count x L x n_ranks)
     DevBuf<unsigned long long> count_ws;   // epx_pooled_count_pass: [histograms (L x n_targets x 256) | NaN counts (L) | prefixes (L x n_targets)]
     int has_last = 0;

@@ -1,6 +1,6 @@
 // Private to libepx.so (host only): what every entry point that post-processes draws has in front of its kernel --
-// epx_named_moments, epx_named_order_stats, epx_pooled_count_pass, epx_predict, epx_loo, epx_draw_diagnostics and
-// epx_pooled_moments.  The draws are those the last sampling call left in c->draws, or `theta` (count, S, P) of the caller,
+// epx_named_moments, epx_named_order_stats, epx_pooled_count_pass, epx_predict, epx_loo, epx_draw_diagnostics,
+// epx_draw_rank_diagnostics and epx_pooled_moments.  The draws are those the last sampling call left in c->draws, or `theta` (count, S, P) of the caller,
 // copied to c->inj.
 // Order of refusals in an entry: its own arguments; for the named entries the name list, then every name in turn; the
 // draw source (draw_source: S, chains, "no draws yet", the sites drawn); whatever the entry derives from S; and only

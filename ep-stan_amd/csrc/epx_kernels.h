@@ -273,6 +273,27 @@ constexpr size_t diag_lds_doubles(int chains, int nkeep, bool in_lds) {
 }
 __global__ void k_draw_diag(DiagArgs a);
 
+// Rank-normalised diagnostics of the draws in device memory (rank_diag.hip; include/epx.h: epx_draw_rank_diagnostics).  A
+// workgroup of EPX_RD_THREADS threads takes one (site, coordinate); lags are computed EPX_RD_LAGS at a time.
+enum { EPX_RD_THREADS = 256, EPX_RD_LAGS = 8 };
+struct RankDiagArgs {
+    int k0, chains, nkeep, P;          // as DiagArgs
+    int d, pg;
+    const int *site_g0;
+    double tau_min;
+    const double *draws;
+    double *out;                       // count x P x EPX_RD_COUNT
+};
+// bytes of dynamic LDS for n used draws: [sort keys (8 n) | series in draw order (8 n) | draw index of a key (4 n)]
+constexpr size_t rank_lds_bytes(int n) { return (size_t)n * 20; }
+__global__ void k_rank_diag(RankDiagArgs a);
+struct RankNormArgs {
+    int n, fold;
+    const double *x;                   // m x n row-major, one series per workgroup
+    double *rank, *z;                  // m x n each
+};
+__global__ void k_rank_normalize(RankNormArgs a);
+
 __global__ void k_cavity(CavityArgs a);
 __global__ void k_moments(MomentArgs a);
 __global__ void k_reweight(ReweightArgs a);

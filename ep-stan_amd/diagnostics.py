@@ -1,13 +1,22 @@
 """Per-coordinate sampler diagnostics of one site's draws in plain NumPy: split-Rhat, effective sample sizes and the
 Monte-Carlo standard error of the tilted mean.  The definition is stated in include/epx.h (enum epx_diag); the device
 kernel k_draw_diag (csrc/draw_diag.hip) computes the same next to the draws.  `diagnostics_host` is the expectation of
-the kernel's tests and `Master.diagnostics`' route on an engine without `draw_diagnostics`."""
+the kernel's tests and `Master.diagnostics`' route on an engine without `draw_diagnostics`.  `rank_diagnostics_host` is
+the same for the rank-normalised split-Rhat, bulk-ESS and tail-ESS (enum epx_rank_diag; kernel k_rank_diag,
+csrc/rank_diag.hip)."""
 
 import numpy as np
+from scipy.special import ndtri
+
+from . import quantiles as _quantiles
 
 # enum epx_diag (include/epx.h): the columns of a diagnostics record
 DG_MEAN, DG_VAR, DG_RHAT, DG_ESS, DG_MCSE, DG_ESS_SQ, DG_COUNT = 0, 1, 2, 3, 4, 5, 6
 DG_NAMES = ('mean', 'var', 'rhat', 'ess', 'mcse', 'ess_sq')
+# enum epx_rank_diag (include/epx.h): the columns of a rank-normalised record
+RD_RHAT, RD_RHAT_BULK, RD_RHAT_FOLD, RD_ESS_BULK, RD_ESS_TAIL, RD_COUNT = 0, 1, 2, 3, 4, 5
+RD_NAMES = ('rhat_rank', 'rhat_bulk', 'rhat_folded', 'ess_bulk', 'ess_tail')
+RD_MAX_DRAWS = 8140            # EPX_RD_MAX_DRAWS (include/epx.h): used draws per site the kernel k_rank_diag takes
 
 
 def split_halves(theta_k, chains):
@@ -79,9 +88,68 @@ def diagnostics_host(theta_k, chains):
     return out
 
 
-def summarise(rec, n):
+def _type7(x, probs):
+    """(len(probs), ...) type-7 quantiles along axis 0 of x (n, ...) in the evaluation form of include/epx.h."""
+    ranks, plan = _quantiles.rank_plan(x.shape[0], probs)
+    return _quantiles.interpolate(_quantiles.order_stats(x, ranks), ranks, plan)
+
+
+def rank_normalize_host(x, fold=False):
+    """(rank, z), each shaped like x: along the LAST axis of x (..., n) the 1-based rank of every value, ties -- equal
+    values, -0.0 and +0.0 among them -- at the average rank of their run, and the normal scores
+    z = ndtri((rank - 3/8) / (n + 1/4)).  fold: of |x - median| (type 7) instead of x.  A series with a non-finite value
+    is NaN throughout.  What k_rank_diag's ranking stage and epx_rank_normalize compute (include/epx.h, enum
+    epx_rank_diag)."""
+    x = np.asarray(x, dtype=np.float64)
+    n = x.shape[-1]
+    flat = x.reshape(-1, n)
+    rank = np.full(flat.shape, np.nan)
+    for i, v in enumerate(flat):
+        if not np.all(np.isfinite(v)):
+            continue
+        if fold:
+            with np.errstate(over='ignore', invalid='ignore'):
+                v = np.abs(v - _type7(v, [0.5])[0])
+        _, inv, cnt = np.unique(v, return_inverse=True, return_counts=True)
+        rank[i] = (np.cumsum(cnt) - (cnt - 1) / 2.0)[inv.ravel()]     # the run's last rank less half its length - 1
+    return rank.reshape(x.shape), ndtri((rank - 0.375) / (n + 0.25)).reshape(x.shape)
+
+
+def rank_diagnostics_host(theta_k, chains):
+    """Rank-normalised record (P, RD_COUNT) of ONE site from its chain-major draws theta_k (S, P), S = chains x nkeep;
+    columns RD_RHAT, RD_RHAT_BULK, RD_RHAT_FOLD, RD_ESS_BULK, RD_ESS_TAIL as include/epx.h (enum epx_rank_diag) defines
+    them, Rhat and ESS being `_geyer`'s.  All five are NaN when nkeep < 4, for a coordinate with a non-finite draw and
+    where the scores have no finite W > 0."""
+    x = split_halves(theta_k, chains)
+    M, h, P = x.shape
+    out = np.full((P, RD_COUNT), np.nan)
+    if h < 2 or P == 0:
+        return out
+    flat = x.reshape(M * h, P)
+    good = np.isfinite(flat).all(axis=0)
+    x = np.where(good, x, 0.0)                               # (a column of zeros: NaN below, like any constant one)
+    flat = x.reshape(M * h, P)
+    with np.errstate(all='ignore'):
+        q05, q95 = _type7(flat, [0.05, 0.95])
+        _, vp, W, ess_bulk = _geyer(rank_normalize_host(flat.T)[1].T.reshape(M, h, P))
+        _, vpf, Wf, ess_fold = _geyer(rank_normalize_host(flat.T, fold=True)[1].T.reshape(M, h, P))
+        tail = np.minimum(_geyer((x <= q05).astype(np.float64))[3], _geyer((x <= q95).astype(np.float64))[3])
+        bulk = np.sqrt(vp / W)
+        fold = np.where(np.isfinite(ess_fold), np.sqrt(vpf / Wf), np.nan)
+        out[:, RD_RHAT] = np.maximum(bulk, fold)             # (NaN where either is)
+        out[:, RD_RHAT_BULK] = bulk
+        out[:, RD_RHAT_FOLD] = fold
+        out[:, RD_ESS_BULK] = ess_bulk
+        out[:, RD_ESS_TAIL] = tail
+    out[~(good & np.isfinite(ess_bulk))] = np.nan
+    return out
+
+
+def summarise(rec, n, rank_rec=None):
     """The dict `Master.diagnostics` returns from the records rec (K, Pmax, DG_COUNT) of all sites (NaN behind a site's
-    own coordinates) and the used draws per site n (K)."""
+    own coordinates) and the used draws per site n (K).  rank_rec (K, Pmax, RD_COUNT): the rank-normalised records; they
+    add `rhat_rank`, `rhat_bulk`, `rhat_folded`, `ess_bulk`, `ess_tail`, `site_max_rhat_rank` (NaN entries skipped; NaN
+    when all are) and `site_min_ess_rank` (the smallest of `ess_bulk` and `ess_tail`) and change nothing else."""
     out = {name: np.ascontiguousarray(rec[:, :, i]) for i, name in enumerate(DG_NAMES)}
     out['n'] = np.asarray(n, dtype=np.int64)
     with np.errstate(invalid='ignore'):
@@ -95,4 +163,11 @@ def summarise(rec, n):
     if not np.isinf(emin).all():
         k = int(np.argmin(emin))
         out['worst'] = (k, int(np.argmin(both[k])))
+    if rank_rec is not None:
+        out.update((name, np.ascontiguousarray(rank_rec[:, :, i])) for i, name in enumerate(RD_NAMES))
+        rmax = np.where(np.isnan(out['rhat_rank']), -np.inf, out['rhat_rank']).max(axis=1)
+        emin = np.minimum(np.where(np.isnan(out['ess_bulk']), np.inf, out['ess_bulk']),
+                          np.where(np.isnan(out['ess_tail']), np.inf, out['ess_tail'])).min(axis=1)
+        out['site_max_rhat_rank'] = np.where(np.isinf(rmax), np.nan, rmax)
+        out['site_min_ess_rank'] = np.where(np.isinf(emin), np.nan, emin)
     return out

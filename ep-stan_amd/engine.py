@@ -624,6 +624,32 @@ class HipEngine(object):
                                             int(chains) if theta is not None else 0, dptr(out), ctypes.byref(n)))
         return (out, n.value) if with_n else out
 
+    def draw_rank_diagnostics(self, k0=0, count=None, theta=None, chains=None, with_n=False):
+        """Rank-normalised diagnostics of the draws of the sites k0..k0+count (epx_draw_rank_diagnostics, include/epx.h):
+        (count, P, 5), columns diagnostics.RD_RHAT, RD_RHAT_BULK, RD_RHAT_FOLD, RD_ESS_BULK, RD_ESS_TAIL; NaN behind a
+        multi-group site's own `site_P[k]` coordinates.  Draws, `theta`, `chains` and `with_n` as `draw_diagnostics`
+        takes them; at most diagnostics.RD_MAX_DRAWS used draws per site."""
+        count = self.K - k0 if count is None else count
+        if theta is not None and chains is None:
+            raise ValueError('injected draws need `chains`')
+        theta, S = self._injected(theta, count)
+        out = np.zeros((max(int(count), 0), self.P, _diagnostics.RD_COUNT))
+        n = ctypes.c_int()
+        check(self.lib.epx_draw_rank_diagnostics(self.ctx, int(k0), int(count), dptr(theta), int(S),
+                                                 int(chains) if theta is not None else 0, dptr(out), ctypes.byref(n)))
+        return (out, n.value) if with_n else out
+
+    def rank_normalize(self, x, fold=False):
+        """(rank, z) of every row of x (m, n) on this engine's device (epx_rank_normalize, the ranking stage of
+        k_rank_diag alone): what diagnostics.rank_normalize_host computes."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] < 1:
+            raise ValueError('x: (m, n) with n >= 1')
+        rank, z = np.zeros(x.shape), np.zeros(x.shape)
+        check(self.lib.epx_rank_normalize(int(self.device), x.shape[0], x.shape[1], dptr(x), 1 if fold else 0,
+                                          dptr(rank), dptr(z)))
+        return rank, z
+
     def pooled_moments(self, center=None, k0=0, count=None, theta=None, want_scatter=True):
         """Moments of the phi draws of the sites k0..k0+count pooled (epx_pooled_moments, include/epx.h): (n, sum, scatter)
         with n the number of draws, sum (d) = sum (x - center) and scatter (d, d) = sum (x - center)(x - center)', None

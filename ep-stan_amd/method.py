@@ -288,15 +288,18 @@ class Worker(object):
         dri[...] = dr
         return ok, float(rec[0, _reweight.RW_KHAT]), float(rec[0, _reweight.RW_WESS])
 
-    def diagnostics(self):
+    def diagnostics(self, rank=False):
         """Per-coordinate diagnostics of the draws of this site's last `tilted` on a stand-alone Worker's own engine:
         the (P, DG_COUNT) record of `diagnostics.diagnostics_host` (columns DG_MEAN, DG_VAR, DG_RHAT, DG_ESS, DG_MCSE,
-        DG_ESS_SQ), computed on the device (epx_draw_diagnostics)."""
+        DG_ESS_SQ), computed on the device (epx_draw_diagnostics).  rank=True: that record and the (P, RD_COUNT) record
+        of `diagnostics.rank_diagnostics_host` (columns RD_RHAT, RD_RHAT_BULK, RD_RHAT_FOLD, RD_ESS_BULK, RD_ESS_TAIL;
+        epx_draw_rank_diagnostics)."""
         if self._master is not None:
             raise RuntimeError("This site belongs to a Master: use Master.diagnostics()")
         if not self._has_sampled:
             raise RuntimeError("Can not diagnose draws before `tilted` has sampled some.")
-        return self._eng.draw_diagnostics(k0=self._k, count=1)[0]
+        rec = self._eng.draw_diagnostics(k0=self._k, count=1)[0]
+        return (rec, self._eng.draw_rank_diagnostics(k0=self._k, count=1)[0]) if rank else rec
 
     def _void_update(self):
         """A chain of this site started at a non-finite density (its draws are its initial point):
@@ -1163,7 +1166,7 @@ class Master(object):
             rec = np.where(code == 1.0, np.nan, np.where(code == 2.0, np.inf, np.where(code == 3.0, -np.inf, rec)))
         return _loo.summarise(rec, S, self.k_lim)
 
-    def diagnostics(self):
+    def diagnostics(self, rank=False):
         """Per-coordinate diagnostics of the tilted draws of the last iteration (include/epx.h, enum epx_diag, states
         the definition): which site's moments rest on few effective draws, and whether `iter` is large enough.  The
         reference reports one number per site, the largest split-Rhat (`mrhats`); it has no counterpart.
@@ -1179,7 +1182,14 @@ class Master(object):
         The draws stay in device memory, the kernel k_draw_diag reduces them to six numbers per coordinate; an engine
         without `draw_diagnostics` (the CPU oracle the tests inject) hands its draws to `diagnostics.diagnostics_host`.
         With several ranks every rank computes its own sites and the records are gathered over the communicator:
-        every rank returns the same result."""
+        every rank returns the same result.
+
+        rank=True adds the rank-normalised diagnostics Stan reports since 2019 (include/epx.h, enum epx_rank_diag; kernel
+        k_rank_diag, or `diagnostics.rank_diagnostics_host` on an engine without `draw_rank_diagnostics`), gathered the
+        same way: `rhat_rank` = max(`rhat_bulk`, `rhat_folded`), `ess_bulk`, `ess_tail`, each (K, Pmax), and
+        `site_max_rhat_rank`, `site_min_ess_rank` (K; the smallest of `ess_bulk` and `ess_tail`).  The folded Rhat sees
+        chains that agree in location and differ in scale, which `rhat` does not; the tail ESS measures the draws the
+        second moments, and so the precision estimate, rest on.  The other entries are those of rank=False."""
         self._need_draws("diagnose draws", "nothing can be diagnosed from them")
         eng, C = self.engine, _diagnostics.DG_COUNT
         chains = int(self.workers[self.k_lo].stan_params['chains'])
@@ -1188,21 +1198,36 @@ class Master(object):
         site_P = eng.d + self._site_ng * pg                      # (K): every site's own coordinates
         Pmax = int(site_P.max())
         rec = np.full((Pmax * C + 1, self.K_local), np.nan, order='F')
-        if hasattr(eng, 'draw_diagnostics'):
-            loc, n = eng.draw_diagnostics(with_n=True)
-        else:
-            loc = np.full((self.K_local, eng.P, C), np.nan)
+
+        def on_the_host(record_of, width):                       # (K_local, P, width) records and the used draws
+            loc = np.full((self.K_local, eng.P, width), np.nan)
             for j in range(self.K_local):
                 Pk = int(site_P[self.k_lo + j])
                 theta = np.ascontiguousarray(eng.get_draws(j, all_params=True))
-                loc[j, :Pk] = _diagnostics.diagnostics_host(theta[:, :Pk], chains)
-            n = 2 * chains * ((theta.shape[0] // chains) // 2)
+                loc[j, :Pk] = record_of(theta[:, :Pk], chains)
+            return loc, 2 * chains * ((theta.shape[0] // chains) // 2)
+
+        if hasattr(eng, 'draw_diagnostics'):
+            loc, n = eng.draw_diagnostics(with_n=True)
+        else:
+            loc, n = on_the_host(_diagnostics.diagnostics_host, C)
         for j in range(self.K_local):
             rec[:eng.P * C, j] = loc[j].ravel()
         rec[-1, :] = n
         full = self.comm.allgather_sites(rec, self.K)
         out = np.ascontiguousarray(full[:-1, :].T).reshape(self.K, Pmax, C)
-        return _diagnostics.summarise(out, np.rint(full[-1, :]).astype(np.int64))
+        rank_out = None
+        if rank:
+            R = _diagnostics.RD_COUNT
+            if hasattr(eng, 'draw_rank_diagnostics'):
+                loc = eng.draw_rank_diagnostics()
+            else:
+                loc, _ = on_the_host(_diagnostics.rank_diagnostics_host, R)
+            rrec = np.full((Pmax * R, self.K_local), np.nan, order='F')
+            for j in range(self.K_local):
+                rrec[:eng.P * R, j] = loc[j].ravel()
+            rank_out = np.ascontiguousarray(self.comm.allgather_sites(rrec, self.K).T).reshape(self.K, Pmax, R)
+        return _diagnostics.summarise(out, np.rint(full[-1, :]).astype(np.int64), rank_out)
 
     # ---- dispatch of the sampling launches: the policy is dispatch.py's, these are its two knobs and what it needs to
     # know of this rank

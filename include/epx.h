@@ -473,6 +473,44 @@ enum epx_diag { EPX_DG_MEAN = 0, EPX_DG_VAR, EPX_DG_RHAT, EPX_DG_ESS, EPX_DG_MCS
 int epx_draw_diagnostics(epx_ctx *ctx, int k0, int count, const double *theta, int S, int chains,
                          double *out /* count * P * EPX_DG_COUNT */, int *nsamp);
 
+/* Rank-normalised split-Rhat, bulk-ESS and tail-ESS of the same draws (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021,
+ * Bayesian Analysis 16(2): what Stan reports since 2019; no counterpart in the reference's own code).  The classic Rhat
+ * above is blind to chains that agree in location and differ in scale, and its ESS needs finite variances; these do not.
+ * The definition, stated once; the kernel k_rank_diag (csrc/rank_diag.hip) and diagnostics.rank_diagnostics_host both
+ * follow it.  Per site and sampled coordinate the used draws are those of epx_draw_diagnostics: M = 2 chains half chains of
+ * length h = nkeep / 2 (an odd nkeep drops the middle draw), n = M h used draws x_i.  Rhat(s) = sqrt(var_plus / W) and
+ * ESS(s) of a series s in the draws' place are EXACTLY the procedure of EPX_DG_RHAT / EPX_DG_ESS above (W, var_plus,
+ * Geyer's initial positive, monotone sequence, the floor 1 / log10(n), no cap).
+ *   Ranks.  r_i is the 1-based rank of x_i among the n used draws; ties are equal VALUES (==: -0.0 and +0.0 tie) and get
+ *     the average rank of their run.  Normal scores z_i = Phi^-1((r_i - 3/8) / (n + 1/4)), evaluated in that form.
+ *   Quantiles q_p of the n used draws: type 7 in the evaluation form of "Posterior quantiles" below; med = q_0.5.
+ *   EPX_RD_RHAT_BULK  Rhat(z);
+ *   EPX_RD_RHAT_FOLD  Rhat(z(zeta)), zeta_i = |x_i - med| rank-normalised the same way: sensitive to the chains' scales;
+ *   EPX_RD_RHAT       max(RHAT_BULK, RHAT_FOLD);
+ *   EPX_RD_ESS_BULK   ESS(z);
+ *   EPX_RD_ESS_TAIL   min(ESS(I(x <= q_0.05)), ESS(I(x <= q_0.95))), the indicators 0.0 / 1.0, not rank-normalised.
+ * Results, never faults: all five are NaN when nkeep < 4, when the coordinate holds any non-finite draw, and when z has no
+ * finite W > 0 (a constant coordinate: every score is exactly 0); RHAT_FOLD and with it RHAT are NaN when z(zeta) has none
+ * (all draws equally far from med); ESS_TAIL is NaN when either indicator's ESS is (an indicator that is constant in every
+ * half chain).  chains == 1 is well defined (M = 2).
+ * out (host): count x P x EPX_RD_COUNT, P the context's record stride; the records behind a multi-group site's own P_k
+ * coordinates are NaN.  theta, S, chains and nsamp as epx_draw_diagnostics takes them, with the same refusals in the same
+ * order.  One workgroup per (site, coordinate) keeps the coordinate's sort keys, the draws they came from and the series
+ * the lag products run on in LDS, 20 bytes per used draw: at most EPX_RD_MAX_DRAWS used draws per site (the 160 KiB of a
+ * compute unit less 1 KiB for the workgroup's other records); more is an error.  The work per coordinate is two sorts of n
+ * keys and, per series, 8 n products for every block of 8 lags its stop rule asks for.  Every sum runs in a fixed order, no
+ * atomics, nothing merged across workgroups: the same bits on every call and for a sub-range of sites.  Stream-ordered, one
+ * launch, one synchronisation. */
+#define EPX_RD_MAX_DRAWS 8140
+enum epx_rank_diag { EPX_RD_RHAT = 0, EPX_RD_RHAT_BULK, EPX_RD_RHAT_FOLD, EPX_RD_ESS_BULK, EPX_RD_ESS_TAIL, EPX_RD_COUNT };
+int epx_draw_rank_diagnostics(epx_ctx *ctx, int k0, int count, const double *theta, int S, int chains,
+                              double *out /* count * P * EPX_RD_COUNT */, int *nsamp);
+/* TEST HOOK, no context: the ranking stage alone, from the device functions k_rank_diag uses.  x (m x n row-major, host):
+ * m series of n values, 1 <= n <= EPX_RD_MAX_DRAWS; fold != 0: |x - med| of each series is ranked instead of x.  rank_out,
+ * z_out (m x n each, host): the average rank and the normal score of every value, in the values' order; NaN throughout a
+ * series with a non-finite value.  Leaves the calling thread's current device as it found it. */
+int epx_rank_normalize(int device, long long m, int n, const double *x, int fold, double *rank_out, double *z_out);
+
 /* Posterior quantiles: order statistics across the draws, per site and over the pool of several sites (no counterpart in
  * the reference, whose user calls `fit.extract` and np.percentile on the host).  The definition, stated once; the kernels
  * k_site_order_stats / k_pooled_count (csrc/quantiles.inc, csrc/order_key.h) and the host restatement (quantiles.py) both
