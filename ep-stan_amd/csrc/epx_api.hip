@@ -1402,33 +1402,22 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
     if (nsamp) *nsamp = src.S;
     if (n == 0) return 0;
     if (!Xn || !out) return fail("epx_predict: Xn and out are required");
-    if (yn && !c->gauss)
-        for (int64_t i = 0; i < n; ++i)
-            if (yn[i] != 0.0 && yn[i] != 1.0)
-                return fail("epx_predict: row %lld: y = %g, the Bernoulli models take 0 or 1", (long long)i, yn[i]);
+    if (yn)
+        if (const int64_t i = bad_response(c, yn, n, false); i >= 0)
+            return fail("epx_predict: row %lld: y = %g, the Bernoulli models take 0 or 1", (long long)i, yn[i]);
     // rows sorted by (site, group), stable: perm[sorted position] = row; then workgroups of <= 64 rows of one (site, group)
-    std::vector<int> perm((size_t)n), at;
+    std::vector<int> perm((size_t)n), first;
     std::vector<PredictWg> wg;
     for (int j = 0; j < count; ++j) {
         const int ng = c->multi ? c->g_cnt[k0 + j] : 1;
-        const int64_t lo = row_lim[j], hi = row_lim[j + 1];
-        at.assign((size_t)ng + 1, 0);
-        for (int64_t i = lo; i < hi; ++i) {
-            const int g = row_group ? row_group[i] : 0;
-            if (g < 0 || g >= ng)
-                return fail("epx_predict: row %lld: group %d outside the %d group(s) of site %d", (long long)i, g, ng, k0 + j);
-            ++at[(size_t)g + 1];
-        }
-        for (int g = 0; g < ng; ++g) {
-            const int first = (int)lo + at[g], rows = at[g + 1];
-            for (int r = 0; r < rows; r += EPX_PR_WG_ROWS)
-                wg.push_back(PredictWg{j, g, first + r, rows - r < EPX_PR_WG_ROWS ? rows - r : (int)EPX_PR_WG_ROWS});
-            at[g + 1] += at[g];
-        }
-        for (int64_t i = lo; i < hi; ++i) perm[(size_t)lo + at[row_group ? row_group[i] : 0]++] = (int)i;
+        if (const int64_t i = sort_rows_by_group(row_lim[j], row_lim[j + 1], row_group, ng, perm.data(), first); i >= 0)
+            return fail("epx_predict: row %lld: group %d outside the %d group(s) of site %d", (long long)i,
+                        row_group ? (int)row_group[i] : 0, ng, k0 + j);
+        for (int g = 0; g < ng; ++g)
+            for (int r = first[g]; r < first[g + 1]; r += EPX_PR_WG_ROWS)
+                wg.push_back(PredictWg{j, g, r, first[g + 1] - r < EPX_PR_WG_ROWS ? first[g + 1] - r : (int)EPX_PR_WG_ROWS});
     }
-    a.model = c->model; a.D = c->D; a.d = c->d; a.gauss = c->gauss; a.P = c->P; a.S = src.S;
-    a.KP = (1 + c->D + 3) / 4 * 4;
+    a.m = predict_model(c); a.S = src.S;
     a.k0 = k0; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
     const size_t nn = (size_t)n, nwg = wg.size();
     HIPCHK(c->pred_ws.grow(nn * D + nn + nn * EPX_PR_COUNT));
@@ -1438,10 +1427,8 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
     static_assert(sizeof(PredictWg) == 4 * sizeof(int), "PredictWg is four ints");
     StreamSync sync{c->stream};          // (`perm` and `wg` are this frame's: the guard is declared behind them)
     if (upload_draws(c, src, &a.draws)) return -1;
-    HIPCHK(hipMemcpyAsync(X_d, Xn, nn * D * 8, hipMemcpyHostToDevice, c->stream));
-    if (yn) HIPCHK(hipMemcpyAsync(y_d, yn, nn * 8, hipMemcpyHostToDevice, c->stream));
+    if (queue_new_rows(c, nn, Xn, yn, perm.data(), X_d, y_d, perm_d)) return -1;
     HIPCHK(hipMemcpyAsync(wg_d, wg.data(), nwg * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(perm_d, perm.data(), nn * sizeof(int), hipMemcpyHostToDevice, c->stream));
     a.wg = reinterpret_cast<const PredictWg *>(wg_d); a.perm = perm_d;
     a.X = X_d; a.y = yn ? y_d : nullptr; a.out = out_d;
     hipLaunchKernelGGL(k_predict, dim3((unsigned)nwg), dim3(256), 0, c->stream, a);
@@ -1465,26 +1452,15 @@ int epx_predict_new_group(epx_ctx *c, int k0, int count, uint64_t seed, long lon
     for (int g = 0; g < G; ++g)
         if (group_label[g] < 0) return fail("%s: group %d: label %d is negative", who, g, (int)group_label[g]);
     // rows sorted by group, stable: perm[sorted position] = row
-    std::vector<int> gfirst((size_t)G + 1, 0), perm((size_t)n), live;
-    for (long long i = 0; i < n; ++i) {
-        const int g = row_group ? row_group[i] : 0;
-        if (g < 0 || g >= G) return fail("%s: row %lld: group %d outside [0,%d)", who, i, g, G);
-        ++gfirst[(size_t)g + 1];
-    }
+    std::vector<int> gfirst, perm((size_t)n), live;
+    if (const int64_t i = sort_rows_by_group(0, n, row_group, G, perm.data(), gfirst); i >= 0)
+        return fail("%s: row %lld: group %d outside [0,%d)", who, (long long)i, row_group ? (int)row_group[i] : 0, G);
     if (yn)
-        for (long long i = 0; i < n; ++i) {
-            if (c->gauss ? !std::isfinite(yn[i]) : (yn[i] != 0.0 && yn[i] != 1.0))
-                return fail("%s: row %lld: y = %g, %s", who, i, yn[i],
-                            c->gauss ? "the Gaussian models take finite responses" : "the Bernoulli models take 0 or 1");
-        }
-    for (int g = 0; g < G; ++g) {
-        if (gfirst[(size_t)g + 1] > 0) live.push_back(g);
-        gfirst[(size_t)g + 1] += gfirst[g];
-    }
-    {
-        std::vector<int> at(gfirst.begin(), gfirst.end() - 1);
-        for (long long i = 0; i < n; ++i) perm[(size_t)at[row_group ? row_group[i] : 0]++] = (int)i;
-    }
+        if (const int64_t i = bad_response(c, yn, n, true); i >= 0)
+            return fail("%s: row %lld: y = %g, %s", who, (long long)i, yn[i],
+                        c->gauss ? "the Gaussian models take finite responses" : "the Bernoulli models take 0 or 1");
+    for (int g = 0; g < G; ++g)
+        if (gfirst[(size_t)g + 1] > gfirst[g]) live.push_back(g);
     NewGroupArgs a;
     DrawSource src;
     if (draw_source(c, who, k0, count, theta, S, nullptr, &src)) return -1;
@@ -1494,8 +1470,7 @@ int epx_predict_new_group(epx_ctx *c, int k0, int count, uint64_t seed, long lon
     a.N = T * R;
     if (N) *N = a.N;
     if (n == 0) return 0;
-    a.model = c->model; a.D = c->D; a.d = c->d; a.gauss = c->gauss; a.P = c->P;
-    a.KP = (1 + c->D + 3) / 4 * 4;
+    a.m = predict_model(c);
     a.E = c->model == EPX_M1B_SG ? 1 : 1 + c->D; a.lap = c->model == EPX_M5B_SG;
     a.R = R; a.t0 = t0; a.seed = seed; a.n = (int)n; a.G = G;
     a.chunk_slabs = newgroup_chunk_slabs(a.N);
@@ -1510,18 +1485,14 @@ int epx_predict_new_group(epx_ctx *c, int k0, int count, uint64_t seed, long lon
     int *perm_d = c->pred_iws, *gfirst_d = perm_d + nn, *label_d = gfirst_d + nG + 1, *live_d = label_d + nG;
     StreamSync sync{c->stream};          // (`perm`, `gfirst` and `live` are this frame's: the guard is declared behind them)
     if (upload_draws(c, src, &a.draws)) return -1;
-    HIPCHK(hipMemcpyAsync(X_d, Xn, nn * D * 8, hipMemcpyHostToDevice, c->stream));
-    if (yn) HIPCHK(hipMemcpyAsync(y_d, yn, nn * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(perm_d, perm.data(), nn * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (queue_new_rows(c, nn, Xn, yn, perm.data(), X_d, y_d, perm_d)) return -1;
     HIPCHK(hipMemcpyAsync(gfirst_d, gfirst.data(), (nG + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(label_d, group_label, nG * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(live_d, live.data(), live.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     a.perm = perm_d; a.gfirst = gfirst_d; a.label = label_d; a.live = live_d;
     a.X = X_d; a.y = yn ? y_d : nullptr;
     a.part_rows = rows_d; a.part_grp = grp_d; a.out = out_d; a.out_group = outg_d;
-    // the grid: every item its own workgroup up to a few per compute unit, then they walk
-    const long long grid_cap = (long long)(c->n_cu > 0 ? c->n_cu : 256) * 4;
-    hipLaunchKernelGGL(k_newgroup, dim3((unsigned)(a.nitem < grid_cap ? a.nitem : grid_cap)), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_newgroup, dim3(walk_grid(c, (size_t)a.nitem, 4)), dim3(256), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     const long long mblocks = ((long long)n + G + 255) / 256;
     hipLaunchKernelGGL(k_newgroup_merge, dim3((unsigned)(mblocks < 65536 ? mblocks : 65536)), dim3(256), 0, c->stream, a);
@@ -1544,8 +1515,7 @@ int epx_loo(epx_ctx *c, int k0, int count, const double *theta, int S, double *o
     if (draw_source(c, "epx_loo", k0, count, theta, S, nullptr, &src)) return -1;
     S = src.S;
     if (nsamp) *nsamp = S;
-    a.p.model = c->model; a.p.D = c->D; a.p.d = c->d; a.p.gauss = c->gauss; a.p.P = c->P; a.p.S = S;
-    a.p.KP = (1 + c->D + 3) / 4 * 4;
+    a.p.m = predict_model(c); a.p.S = S;
     a.p.k0 = k0; a.p.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
     a.p.perm = nullptr; a.p.y = nullptr; a.p.out = nullptr; a.p.X = c->X;
     a.y8 = c->y; a.yd = c->yd;
@@ -1558,7 +1528,7 @@ int epx_loo(epx_ctx *c, int k0, int count, const double *theta, int S, double *o
         const long long v = atoll(e);
         if (v >= 0 && (size_t)v < cap) cap = (size_t)v;
     }
-    const size_t fixed = ((size_t)a.p.KP * 16 + 32) * 8 + psis_lds_bytes(a.M), tile = (size_t)16 * a.stride * 8;
+    const size_t fixed = ((size_t)a.p.m.KP * 16 + 32) * 8 + psis_lds_bytes(a.M), tile = (size_t)16 * a.stride * 8;
     if (a.mfit > PSIS_FIT_MAX || fixed > LDS_CAP - 1024)
         return fail("epx_loo: S = %d draws: the tail of %d draws per row does not fit the LDS", S, a.M);
     a.tiles = fixed + 4 * tile <= cap ? 4 : fixed + 2 * tile <= cap ? 2 : fixed + tile <= cap ? 1 : 0;
@@ -1581,9 +1551,7 @@ int epx_loo(epx_ctx *c, int k0, int count, const double *theta, int S, double *o
     if (c->N > 0x7fffffff) return fail("epx_loo: %lld rows, at most 2^31 - 1", (long long)c->N);
     a.row0 = c->k_lim[k0];
     const size_t rows = (size_t)(c->k_lim[k0 + count] - c->k_lim[k0]), nwg = wg.size();
-    // the grid: every item its own workgroup up to a few per compute unit (the LDS holds one or two), then they walk
-    const size_t grid_cap = (size_t)(c->n_cu > 0 ? c->n_cu : 256) * (in_lds ? 4 : 2);
-    const unsigned grid = (unsigned)(nwg < grid_cap ? nwg : grid_cap);
+    const unsigned grid = walk_grid(c, nwg, in_lds ? 4 : 2);       // (the LDS holds one or two workgroups per compute unit)
     const size_t n_out = rows * EPX_LO_COUNT, n_slab = in_lds ? 0 : (size_t)grid * item * a.stride;
     HIPCHK(c->loo_ws.grow(n_out + n_slab));
     HIPCHK(c->pred_iws.grow(4 * nwg));

@@ -1,12 +1,16 @@
 // Private to libepx.so (host only): what every entry point that post-processes draws has in front of its kernel --
-// epx_named_moments, epx_named_order_stats, epx_pooled_count_pass, epx_predict, epx_loo, epx_draw_diagnostics,
-// epx_draw_rank_diagnostics and epx_pooled_moments.  The draws are those the last sampling call left in c->draws, or `theta` (count, S, P) of the caller,
-// copied to c->inj.
+// epx_named_moments, epx_named_order_stats, epx_pooled_count_pass, epx_predict, epx_predict_new_group, epx_loo,
+// epx_draw_diagnostics, epx_draw_rank_diagnostics and epx_pooled_moments.  The draws are those the last sampling call
+// left in c->draws, or `theta` (count, S, P) of the caller, copied to c->inj.  Behind them: what the predictive entries
+// (epx_predict, epx_predict_new_group, epx_loo) share in front of the row-tile walk of predict_tile.h.
 // Order of refusals in an entry: its own arguments; for the named entries the name list, then every name in turn; the
 // draw source (draw_source: S, chains, "no draws yet", the sites drawn); whatever the entry derives from S; and only
 // then the first copy (upload_draws), behind a StreamSync (epx_ctx.h) -- from there on every exit has synchronised c->stream,
 // because the queued copies read the caller's memory.
 #pragma once
+#include <cmath>
+#include <vector>
+
 #include "epx_ctx.h"
 #include "epx_kernels.h"
 
@@ -79,6 +83,51 @@ inline int named_front(const epx_ctx *c, const char *who, int k0, int count, con
     if (draw_source(c, who, k0, count, theta, S, nullptr, src)) return -1;
     a.S = src->S;
     return 0;
+}
+
+// ---- the predictive entries
+inline PredictModel predict_model(const epx_ctx *c) {
+    return PredictModel{c->model, c->D, c->d, c->gauss, c->P, (1 + c->D + 3) / 4 * 4};
+}
+
+// The first row of [0, n) whose response the family does not take, or -1.  Bernoulli: 0 or 1; Gaussian: anything, or
+// with `finite` (a new group's joint term adds the rows' terms up) finite values only.
+inline int64_t bad_response(const epx_ctx *c, const double *yn, int64_t n, bool finite) {
+    for (int64_t i = 0; i < n; ++i)
+        if (c->gauss ? finite && !std::isfinite(yn[i]) : (yn[i] != 0.0 && yn[i] != 1.0)) return i;
+    return -1;
+}
+
+// Stable counting sort of the rows [lo, hi) by their group in [0, ng) (row_group NULL: all in group 0): the rows of
+// group g, in their order, are perm[first[g]] .. perm[first[g + 1]], first[0] = lo.  Returns the first row whose group
+// is out of range (nothing of perm is written then), or -1.
+inline int64_t sort_rows_by_group(int64_t lo, int64_t hi, const int32_t *row_group, int ng, int *perm, std::vector<int> &first) {
+    first.assign((size_t)ng + 1, 0);
+    for (int64_t i = lo; i < hi; ++i) {
+        const int g = row_group ? row_group[i] : 0;
+        if (g < 0 || g >= ng) return i;
+        ++first[(size_t)g + 1];
+    }
+    first[0] = (int)lo;
+    for (int g = 0; g < ng; ++g) first[(size_t)g + 1] += first[g];
+    std::vector<int> at(first.begin(), first.end() - 1);
+    for (int64_t i = lo; i < hi; ++i) perm[at[row_group ? row_group[i] : 0]++] = (int)i;
+    return -1;
+}
+
+// Queues the copies of the n new rows, their responses (if any) and the sort's perm; behind a StreamSync
+inline int queue_new_rows(epx_ctx *c, size_t n, const double *Xn, const double *yn, const int *perm, double *X_d, double *y_d,
+                          int *perm_d) {
+    HIPCHK(hipMemcpyAsync(X_d, Xn, n * c->D * 8, hipMemcpyHostToDevice, c->stream));
+    if (yn) HIPCHK(hipMemcpyAsync(y_d, yn, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(perm_d, perm, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+// The grid of a kernel whose workgroups walk their items: every item its own workgroup up to per_cu per compute unit
+inline unsigned walk_grid(const epx_ctx *c, size_t items, int per_cu) {
+    const size_t cap = (size_t)(c->n_cu > 0 ? c->n_cu : 256) * per_cu;
+    return (unsigned)(items < cap ? items : cap);
 }
 
 }  // namespace epx

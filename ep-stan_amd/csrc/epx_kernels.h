@@ -179,9 +179,13 @@ __global__ void k_pooled_final(PooledArgs a);
 // sorts the new rows by (site, group) and cuts them into workgroups of at most 64 rows of ONE (site, group).
 enum { EPX_PR_TILE = 16, EPX_PR_WG_ROWS = 64, EPX_PR_DMAX = 128 };
 struct PredictWg { int site, group, first, rows; };   // site of the call; first sorted row; rows <= EPX_PR_WG_ROWS
-struct PredictArgs {
-    int model, D, d, gauss, P, S;
+struct PredictModel {                  // what the predictive kernels know of the context's model (predict_tile.h)
+    int model, D, d, gauss, P;
     int KP;                            // 1 + D (alpha's leading 1 and the D columns) rounded up to a multiple of 4
+};
+struct PredictArgs {
+    PredictModel m;
+    int S;
     int k0;                            // first site (absolute: indexes site_g0)
     const int *site_g0;                // prefix sums of the groups per site, or NULL: one group everywhere
     const double *draws;               // site b of the call at draws + b * S * P: (S, P) row-major
@@ -203,9 +207,8 @@ constexpr int newgroup_chunk_slabs(long long N) {
     return (int)(want < EPX_NGP_MIN_SLABS ? EPX_NGP_MIN_SLABS : want > EPX_NGP_MAX_SLABS ? EPX_NGP_MAX_SLABS : want);
 }
 struct NewGroupArgs {
-    int model, D, d, gauss, P;
-    int KP;                            // 1 + D rounded up to a multiple of 4 (PredictArgs)
-    int E, lap;                        // latents per member: 1 (m1) or 1 + D; m5: Laplace instead of normal
+    PredictModel m;
+    int E, lap;                       // latents per member: 1 (m1) or 1 + D; m5: Laplace instead of normal
     int R, chunk_slabs;
     long long N, t0;                   // pool members; pooled index of the first draw of the call
     long long nchunk, nitem;           // chunks of the pool; work items = groups with rows x nchunk

@@ -6,18 +6,16 @@
 // samplers' Philox stream at kind K_NEWGROUP, keyed by the group's label: a function of (seed, label, t, r, e) alone.
 //
 // k_newgroup.  A work item is (new group, chunk of the pool): chunks are newgroup_chunk_slabs(N) slabs of 16 members, a
-// function of N alone.  The workgroup walks the group's rows in blocks of 64 (a tile of 16 per wave, the A operand in
-// registers as in k_predict) and, per block, the chunk's slabs twice:
-//   - all 256 threads stage the slab: a thread = (member tid & 15, Box-Muller / Laplace pair tid >> 4, + 16, ...) draws
-//     the pair's two latents and writes coef[k][member], k = 0 alpha, k = 1 + j beta_j (named_elem_of's transforms at
-//     one group, the latent in the place of the sampled eta / etb), zeros behind 1 + D and behind the last member;
-//   - every wave multiplies its row tile by the slab (predict_product) and applies predict_link.
-// Pass 1: chunk-local sums of f and of the link's value, the largest ll of every row -- and, with responses, the sum of
-// ll over the block's rows per member: lane -> LDS -> 16 threads add the 16 partial sums of a member (4 waves x 4 row
-// quarters) in a fixed order onto gll[member], block after block: the group's JOINT log-likelihood under the member's
-// shared latents.  Pass 2 regenerates the slabs (the same bits: the stream is counter-based) for the centred squares
-// and sum exp(ll - max).  The row's chunk record [mean, f mean, M2, log-mean-exp] goes to the workspace; behind the
-// last block the 256 threads reduce gll to the chunk's log-mean-exp of the joint term.
+// function of N alone.  The workgroup walks the group's rows in blocks of 64 and, per block, the chunk's slabs twice:
+// the row-tile walk of predict_tile.h, a slab column being a pool member.  This file adds where a slab comes from
+// (newgroup_stage): a thread = (member tid & 15, Box-Muller / Laplace pair tid >> 4, + 16, ...) draws the pair's two
+// latents and writes coef[k][member] by named_elem_of's transforms at one group, the latent in the place of the sampled
+// eta / etb.  And, with responses, what pass 1 does beside the walk's sums: the sum of ll over the block's rows per
+// member, lane -> LDS -> 16 threads add the 16 partial sums of a member (4 waves x 4 row quarters) in a fixed order onto
+// gll[member], block after block: the group's JOINT log-likelihood under the member's shared latents.  Pass 2
+// regenerates the slabs (the same bits: the stream is counter-based).  The row's chunk record [mean, f mean, M2,
+// log-mean-exp] goes to the workspace; behind the last block the 256 threads reduce gll to the chunk's log-mean-exp of
+// the joint term.
 // k_newgroup_merge adds the chunk records of a row, or of a group, in ascending chunk order with the merge rules of the
 // definition.  No atomics anywhere; the bits of a row's record depend on the row, the group's label and the pool only,
 // those of a group's joint term on the group's rows in the call's order.
@@ -54,54 +52,25 @@ __device__ inline double newgroup_value(const NamedElem &el, const double *th, d
 }
 
 // The coefficient block of the slab of members m0 .. m0 + 15 (those below m_hi)
-__device__ inline void newgroup_stage(const NewGroupArgs &a, RngKey key, long long m0, long long m_hi, double *coef,
-                                      double *lsig, double *sig) {
+__device__ inline void newgroup_stage(const NewGroupArgs &a, RngKey key, long long m0, long long m_hi, const Slab &sl) {
     const int tid = threadIdx.x, c = tid & 15;
     const long long m = m0 + c;
     const bool in = m < m_hi;
     const long long bs = in ? m / a.R : 0;               // site-major draw of the call
     const uint32_t r = (uint32_t)(in ? m - bs * a.R : 0), t = (uint32_t)(a.t0 + bs);
-    const double *th = a.draws + (size_t)bs * a.P;
-    for (int p = tid >> 4; 2 * p < a.KP; p += 16) {
+    const double *th = a.draws + (size_t)bs * a.m.P;
+    for (int p = tid >> 4; 2 * p < a.m.KP; p += 16) {
         double z[2] = {0.0, 0.0};
         if (in && 2 * p < a.E) newgroup_pair(key, t, r, p, a.lap, z[0], z[1]);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int k = 2 * p + h;
             double v = 0.0;
-            if (in && k <= a.D) {
-                const NamedElem el = k == 0 ? named_elem_of(EPX_NM_ALPHA, 0, a.model, a.D, a.d, a.gauss, 1)
-                                            : named_elem_of(EPX_NM_BETA, k - 1, a.model, a.D, a.d, a.gauss, 1);
-                v = newgroup_value(el, th, z[h]);
-            }
-            coef[k * 16 + c] = v;
+            if (in && k <= a.m.D) v = newgroup_value(tile_coef_elem(a.m, k, 0, 1), th, z[h]);
+            sl.coef[k * 16 + c] = v;
         }
     }
-    if (a.gauss && tid < 16) {                           // y ~ normal(f, sigma), sigma = exp(phi[0])
-        const double ls = in ? th[0] : 0.0;
-        lsig[tid] = ls;
-        sig[tid] = exp_d(ls);
-    }
-}
-
-// max / sum over the workgroup of a value per thread, in a fixed order: 16 lanes by DPP, the 16 rows through LDS
-__device__ inline double newgroup_wg_max(double v, double *scr) {
-    v = row16_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 15) == 0) scr[threadIdx.x >> 4] = v;
-    __syncthreads();
-    double o = scr[0];
-    for (int i = 1; i < 16; ++i) o = fmax(o, scr[i]);
-    return o;
-}
-__device__ inline double newgroup_wg_sum(double v, double *scr) {
-    v = row16_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 15) == 0) scr[threadIdx.x >> 4] = v;
-    __syncthreads();
-    double o = scr[0];
-    for (int i = 1; i < 16; ++i) o += scr[i];
-    return o;
+    tile_stage_scale(a.m, th, in, sl.lsig, sl.sig);
 }
 
 __global__ void __launch_bounds__(256)
@@ -111,10 +80,11 @@ k_newgroup(NewGroupArgs a) {
     __shared__ double part[256];                          // pass 1: a lane's sum of ll over its rows, per slab
     __shared__ double gll[EPX_NGP_MAX_SLABS * 16];        // the chunk's members: sum of ll over the group's rows
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 15, kq = lane >> 4;
-    const int D = a.D, nstep = a.KP / 4;
+    const int gauss = a.m.gauss, nstep = a.m.KP / 4;
     const int t0 = wave * EPX_PR_TILE;
     const bool has_y = a.y != nullptr;
     const long long chunk = (long long)a.chunk_slabs * 16;
+    const Slab sl{coef, lsig, sig};
 
     for (long long wi = blockIdx.x; wi < a.nitem; wi += gridDim.x) {
         const int g = a.live[wi / a.nchunk];
@@ -128,101 +98,33 @@ k_newgroup(NewGroupArgs a) {
         for (int rb = 0; rb < grows; rb += EPX_PR_WG_ROWS) {
             const int first = gfirst + rb, rows = grows - rb < EPX_PR_WG_ROWS ? grows - rb : (int)EPX_PR_WG_ROWS;
             const bool busy = t0 < rows;                  // (wave-uniform: a wave without rows only stages)
-            // A operand: lane = (row col, k kq) of every step; column 0 of the tile is the 1 that takes alpha
-            double xa[PR_STEPS];
-#pragma unroll
-            for (int i = 0; i < PR_STEPS; ++i) xa[i] = 0.0;
-            if (busy && t0 + col < rows) {
-                const double *x = a.X + (size_t)a.perm[first + t0 + col] * D;
-#pragma unroll
-                for (int i = 0; i < PR_STEPS; ++i) {
-                    const int c = 4 * i + kq;
-                    if (c <= D) xa[i] = c == 0 ? 1.0 : x[c - 1];
-                }
-            }
-            // results: lane = (rows kq + 4 r, member col)
-            int srow[4];                                  // sorted position of the row, or -1
-            double yv[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int tr = t0 + kq + 4 * r;
-                srow[r] = busy && tr < rows ? first + tr : -1;
-                yv[r] = has_y && srow[r] >= 0 ? a.y[a.perm[srow[r]]] : 0.0;
-            }
-
-            // ---- pass 1: sums of f and of the link's value, the largest ll; the members' sums of ll over the rows
-            double sf[4] = {0.0, 0.0, 0.0, 0.0}, sm[4] = {0.0, 0.0, 0.0, 0.0};
-            double mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+            RowTile t;
+            tile_load(t, a.X, a.m.D, a.perm, first, rows, t0, busy, has_y, [&](size_t row) { return a.y[row]; });
+            RowSums sums;
+            sums_begin(sums);
+            // ---- pass 1, and the members' sums of ll over the block's rows onto gll
             for (long long m0 = m_lo; m0 < m_hi; m0 += 16) {
-                newgroup_stage(a, key, m0, m_hi, coef, lsig, sig);
-                __syncthreads();
                 double lsum = 0.0;
-                if (busy) {
-                    const v4d f = predict_product(xa, coef, nstep, lane);
-                    if (m0 + col < m_hi) {
-                        const double ls = a.gauss ? lsig[col] : 0.0, sg = a.gauss ? sig[col] : 1.0;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            double mu, ll;
-                            predict_link(a.gauss, f[r], yv[r], ls, sg, mu, ll);
-                            sf[r] += f[r];
-                            sm[r] += mu;
-                            mx[r] = fmax(mx[r], ll);
-                            if (srow[r] >= 0) lsum += ll;
-                        }
-                    }
-                }
-                if (has_y) part[tid] = lsum;
-                __syncthreads();
+                tile_slab(t, sl, gauss, nstep, busy, m0 + col < m_hi, true, [&] { newgroup_stage(a, key, m0, m_hi, sl); },
+                          [&](int r, double f, double mu, double ll) {
+                              sums_add1(sums, r, f, mu, ll);
+                              if (t.row[r] >= 0) lsum += ll;
+                          },
+                          [&] { if (has_y) part[tid] = lsum; });
                 if (has_y && tid < 16) {                  // member tid of the slab: waves 0..3, row quarters 0..3, in order
                     double s = 0.0;
                     for (int i = 0; i < 16; ++i) s += part[i * 16 + tid];
                     gll[(int)(m0 - m_lo) + tid] += s;
                 }
             }
-            double fm[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                fm[r] = row16_sum(sf[r]) / Nc;
-                sm[r] = row16_sum(sm[r]) / Nc;
-                mx[r] = row16_max(mx[r]);
-            }
-
-            // ---- pass 2: centred squares of f, sum exp(ll - max)
-            double q[4] = {0.0, 0.0, 0.0, 0.0}, se[4] = {0.0, 0.0, 0.0, 0.0};
-            for (long long m0 = m_lo; m0 < m_hi; m0 += 16) {
-                newgroup_stage(a, key, m0, m_hi, coef, lsig, sig);
-                __syncthreads();
-                if (busy) {
-                    const v4d f = predict_product(xa, coef, nstep, lane);
-                    if (m0 + col < m_hi) {
-                        const double ls = a.gauss ? lsig[col] : 0.0, sg = a.gauss ? sig[col] : 1.0;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const double c = f[r] - fm[r];
-                            q[r] += c * c;
-                            if (has_y) {
-                                double mu, ll;
-                                predict_link(a.gauss, f[r], yv[r], ls, sg, mu, ll);
-                                se[r] += exp_d(ll - mx[r]);
-                            }
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                q[r] = row16_sum(q[r]);
-                se[r] = row16_sum(se[r]);
-                if (col == 0 && srow[r] >= 0) {
-                    double *o = a.part_rows + ((size_t)ch * a.n + srow[r]) * EPX_PR_COUNT;
-                    o[EPX_PR_MEAN] = sm[r];
-                    o[EPX_PR_F_MEAN] = fm[r];
-                    o[EPX_PR_F_M2] = q[r];
-                    o[EPX_PR_LPD] = has_y ? mx[r] + log_pos_d(se[r] / Nc) : NAN;
-                }
-            }
+            sums_close1(sums, Nc);
+            // ---- pass 2; the row's chunk record goes to its sorted position
+            for (long long m0 = m_lo; m0 < m_hi; m0 += 16)
+                tile_slab(t, sl, gauss, nstep, busy, m0 + col < m_hi, has_y, [&] { newgroup_stage(a, key, m0, m_hi, sl); },
+                          [&](int r, double f, double mu, double ll) { sums_add2(sums, r, f, ll, has_y); }, [] {});
+            sums_close2(sums, t, Nc, has_y, [&](int r) {
+                return a.part_rows + ((size_t)ch * a.n + first + t0 + kq + 4 * r) * EPX_PR_COUNT;
+            });
         }
 
         // ---- the group's joint term of the chunk: log-mean-exp of gll about its largest entry
@@ -231,10 +133,10 @@ k_newgroup(NewGroupArgs a) {
             const int nm = (int)(m_hi - m_lo);
             double top = -INFINITY;
             for (int i = tid; i < nm; i += 256) top = fmax(top, gll[i]);
-            top = newgroup_wg_max(top, scr);
+            top = wg_reduce(row16_max(top), scr, [](double x, double y) { return fmax(x, y); });
             double s = 0.0;
             for (int i = tid; i < nm; i += 256) s += exp_d(gll[i] - top);
-            s = newgroup_wg_sum(s, scr);
+            s = wg_reduce(row16_sum(s), scr, [](double x, double y) { return x + y; });
             if (tid == 0) a.part_grp[(size_t)ch * a.G + g] = top + log_pos_d(s / Nc);
         }
         __syncthreads();                                  // the next item zeroes gll

@@ -515,6 +515,22 @@ class HipEngine(object):
                                          dptr(theta), int(S), dptr(mean), dptr(m2), ctypes.byref(n)))
         return n.value, self._cut_sites(names, lens, mean, k0), self._cut_sites(names, lens, m2, k0)
 
+    def _new_rows(self, Xn, n, group, group_name, y):
+        """Xn (n, D) -- n None: any -- as float64, one int32 group per row (or None) and one float64 response per row (or
+        None) of predict / predict_new_group."""
+        Xn = np.ascontiguousarray(Xn, dtype=np.float64)
+        if Xn.ndim != 2 or Xn.shape[1] != self.D or (n is not None and Xn.shape[0] != n):
+            raise ValueError('Xn: (n, D) = ({}, {})'.format('n' if n is None else n, self.D))
+        if group is not None:
+            group = np.ascontiguousarray(group, dtype=np.int32)
+            if group.shape != (Xn.shape[0],):
+                raise ValueError(group_name + ': one group per new row')
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.float64)
+            if y.shape != (Xn.shape[0],):
+                raise ValueError('y: one response per new row')
+        return Xn, group, y
+
     def predict(self, Xn, row_lim, row_group=None, y=None, k0=0, count=None, theta=None):
         """Posterior predictive of new rows (epx_predict, include/epx.h): (n, 4), columns site_params.PR_MEAN,
         PR_F_MEAN, PR_F_M2, PR_LPD (NaN without y).  Xn (n, D); the rows of site k0 + j are
@@ -524,18 +540,7 @@ class HipEngine(object):
         row_lim = np.ascontiguousarray(row_lim, dtype=np.int64)
         if row_lim.shape != (count + 1,):
             raise ValueError('row_lim: count + 1 = {} row limits'.format(count + 1))
-        n = int(row_lim[-1])
-        Xn = np.ascontiguousarray(Xn, dtype=np.float64)
-        if Xn.ndim != 2 or Xn.shape[1] != self.D or Xn.shape[0] != n:
-            raise ValueError('Xn: (n, D) = ({}, {})'.format(n, self.D))
-        if row_group is not None:
-            row_group = np.ascontiguousarray(row_group, dtype=np.int32)
-            if row_group.shape != (Xn.shape[0],):
-                raise ValueError('row_group: one group per new row')
-        if y is not None:
-            y = np.ascontiguousarray(y, dtype=np.float64)
-            if y.shape != (Xn.shape[0],):
-                raise ValueError('y: one response per new row')
+        Xn, row_group, y = self._new_rows(Xn, int(row_lim[-1]), row_group, 'row_group', y)
         theta, S = self._injected(theta, count)
         out = np.zeros((Xn.shape[0], _site_params.PR_COUNT))
         check(self.lib.epx_predict(self.ctx, int(k0), int(count), row_lim.ctypes.data_as(_lib.c_int64_p),
@@ -551,19 +556,9 @@ class HipEngine(object):
         first draw.  The draws are those of the last sampling call, on the device; `theta` (count, S, P) injects
         draws instead (test hook)."""
         count = self.K - k0 if count is None else count
-        Xn = np.ascontiguousarray(Xn, dtype=np.float64)
-        if Xn.ndim != 2 or Xn.shape[1] != self.D:
-            raise ValueError('Xn: (n, D) = (n, {})'.format(self.D))
+        Xn, gidx, y = self._new_rows(Xn, None, gidx, 'gidx', y)
         n = Xn.shape[0]
         labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
-        if gidx is not None:
-            gidx = np.ascontiguousarray(gidx, dtype=np.int32)
-            if gidx.shape != (n,):
-                raise ValueError('gidx: one group per new row')
-        if y is not None:
-            y = np.ascontiguousarray(y, dtype=np.float64)
-            if y.shape != (n,):
-                raise ValueError('y: one response per new row')
         theta, S = self._injected(theta, count)
         G = labels.shape[0]
         out = np.zeros((n, _site_params.PR_COUNT))

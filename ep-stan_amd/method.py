@@ -928,6 +928,38 @@ class Master(object):
             return result[0]
         return result
 
+    def _new_rows(self, X_new):
+        """`X_new` of predict / predict_new_group as float64 (n, D)."""
+        X_new = np.asarray(X_new, dtype=np.float64)
+        if X_new.ndim != 2 or X_new.shape[1] != self.D:
+            raise ValueError("Argument `X_new` should be two dimensional with {} columns".format(self.D))
+        return X_new
+
+    def _new_responses(self, y_new, n, finite):
+        """`y_new` of predict / predict_new_group as contiguous float64 (n,), or None.  The Bernoulli models take 0 or
+        1; the Gaussian ones anything, or with `finite` (a new group's joint term adds its rows' terms up) finite
+        values only."""
+        if y_new is None:
+            return None
+        ys = np.ascontiguousarray(y_new, dtype=np.float64)
+        if ys.shape != (n,):
+            raise ValueError("The shapes of `y_new` and `X_new` does not match")
+        gauss = self._site_spec()[1]
+        if gauss and not finite:
+            return ys
+        bad = np.nonzero(~np.isfinite(ys) if gauss else (ys != 0) & (ys != 1))[0]
+        if bad.size:
+            raise ValueError("`y_new` of row {}: {}; site model {!r} takes {}".format(
+                int(bad[0]), ys[bad[0]], self.model_name, "finite responses" if gauss else "responses 0 or 1"))
+        return ys
+
+    @staticmethod
+    def _predictive_result(rec, has_y, n, **more):
+        """The result of predict / predict_new_group from the records `rec` (rows, 4) over n draws or pool members."""
+        return dict(mean=rec[:, _site_params.PR_MEAN].copy(), f_mean=rec[:, _site_params.PR_F_MEAN].copy(),
+                    f_var=rec[:, _site_params.PR_F_M2] / (n - 1),
+                    lpd=rec[:, _site_params.PR_LPD].copy() if has_y else None, **more, n=n)
+
     def _local_predict(self, Xn, row_lim, group, y):
         """Prediction records (n_local, 4) of new rows of this rank's sites (see HipEngine.predict).  The device engine
         computes them next to the draws; an engine without `predict` (the CPU oracle the tests inject) hands its draws
@@ -964,9 +996,7 @@ class Master(object):
         self._need_draws("predict", "nothing can be predicted from them")
         if (site_sizes is None) == (site_ind is None):
             raise ValueError("Give exactly one of `site_sizes` and `site_ind`")
-        X_new = np.asarray(X_new, dtype=np.float64)
-        if X_new.ndim != 2 or X_new.shape[1] != self.D:
-            raise ValueError("Argument `X_new` should be two dimensional with {} columns".format(self.D))
+        X_new = self._new_rows(X_new)
         n, K = X_new.shape[0], self.K
         order = None
         if site_sizes is not None:
@@ -1001,16 +1031,9 @@ class Master(object):
                 k = int(np.searchsorted(lim, i, side='right') - 1)
                 raise ValueError("`j_ind` of row {}: group {} outside 1..{} of site {}"
                                  .format(int(rows[i]), int(group[i]) + 1, int(self._site_ng[k]), k))
-        ys = None
-        if y_new is not None:
-            y_new = np.asarray(y_new, dtype=np.float64)
-            if y_new.shape != (n,):
-                raise ValueError("The shapes of `y_new` and `X_new` does not match")
-            bad = np.nonzero((y_new != 0) & (y_new != 1))[0]
-            if not gauss and bad.size:
-                raise ValueError("`y_new` of row {}: {}; site model {!r} takes responses 0 or 1"
-                                 .format(int(bad[0]), y_new[bad[0]], self.model_name))
-            ys = np.ascontiguousarray(y_new[rows])
+        ys = self._new_responses(y_new, n, finite=False)
+        if ys is not None:
+            ys = np.ascontiguousarray(ys[rows])
         Xs = np.ascontiguousarray(X_new[rows])
         lo, hi = int(lim[self.k_lo]), int(lim[self.k_hi])
         rec = np.zeros((n, _site_params.PR_COUNT))
@@ -1022,10 +1045,7 @@ class Master(object):
             rec = self.comm.allreduce_sum(rec)
         out = np.empty_like(rec)
         out[rows] = rec
-        S = self.engine.num_draws()
-        return dict(mean=out[:, _site_params.PR_MEAN].copy(), f_mean=out[:, _site_params.PR_F_MEAN].copy(),
-                    f_var=out[:, _site_params.PR_F_M2] / (S - 1),
-                    lpd=out[:, _site_params.PR_LPD].copy() if ys is not None else None, n=S)
+        return self._predictive_result(out, ys is not None, self.engine.num_draws())
 
     def _local_predict_new_group(self, Xn, gidx, labels, y, seed, R):
         """(rows (n, 4), glpd (G,), N) of new groups against this rank's sites' draws (see HipEngine.predict_new_group).
@@ -1057,9 +1077,7 @@ class Master(object):
         several ranks every rank runs all rows against its own sites' draws, and one collective of a rank-slotted
         record followed by newgroup.merge in rank order makes every rank return the same result."""
         self._need_draws("predict a new group", "nothing can be predicted from them")
-        X_new = np.asarray(X_new, dtype=np.float64)
-        if X_new.ndim != 2 or X_new.shape[1] != self.D:
-            raise ValueError("Argument `X_new` should be two dimensional with {} columns".format(self.D))
+        X_new = self._new_rows(X_new)
         n = X_new.shape[0]
         if group is None:
             group = np.zeros(n, dtype=np.int64)
@@ -1073,16 +1091,7 @@ class Master(object):
             raise ValueError("`R`: an integer number of replicates in 1..{}".format(_newgroup.R_MAX))
         if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
             raise ValueError("`seed`: an integer in [0, 2^64)")
-        mid, gauss, _ = self._site_spec()
-        ys = None
-        if y_new is not None:
-            ys = np.ascontiguousarray(y_new, dtype=np.float64)
-            if ys.shape != (n,):
-                raise ValueError("The shapes of `y_new` and `X_new` does not match")
-            bad = np.nonzero(~np.isfinite(ys) if gauss else (ys != 0) & (ys != 1))[0]
-            if bad.size:
-                raise ValueError("`y_new` of row {}: {}; site model {!r} takes {}".format(
-                    int(bad[0]), ys[bad[0]], self.model_name, "finite responses" if gauss else "responses 0 or 1"))
+        ys = self._new_responses(y_new, n, finite=True)
         S = self.engine.num_draws()
         if self.K * S > 2 ** 32:
             raise ValueError("{} sites x {} draws: more than 2^32 pooled draws".format(self.K, S))
@@ -1101,10 +1110,8 @@ class Master(object):
             parts = [(rec[r, :n * _site_params.PR_COUNT].reshape(n, _site_params.PR_COUNT),
                       rec[r, n * _site_params.PR_COUNT:-1], int(round(rec[r, -1]))) for r in range(world)]
             rows, glpd, N = _newgroup.merge(parts)
-        return dict(mean=rows[:, _site_params.PR_MEAN].copy(), f_mean=rows[:, _site_params.PR_F_MEAN].copy(),
-                    f_var=rows[:, _site_params.PR_F_M2] / (N - 1),
-                    lpd=rows[:, _site_params.PR_LPD].copy() if ys is not None else None,
-                    groups=labels.astype(np.int64), group_lpd=np.array(glpd) if ys is not None else None, n=N)
+        return self._predictive_result(rows, ys is not None, N, groups=labels.astype(np.int64),
+                                       group_lpd=np.array(glpd) if ys is not None else None)
 
     def _local_loo(self):
         """Leave-one-out records (rows of this rank's sites, 6) and the draws per site (see HipEngine.loo).  The device

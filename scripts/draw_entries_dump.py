@@ -2,7 +2,8 @@
 """Every array the entries over draws return, saved for a bit-for-bit comparison of two builds of libepx.so on one device:
 HipEngine.named_moments, named_order_stats, pooled_count_pass, predict, loo, draw_diagnostics and pooled_moments at the
 shapes of their tests/test_gpu_*.py files -- injected draws of single-group and multi-group models, and the sampler's own
-draws of a short run (whole range and a sub-range) -- with fixed seeds.
+draws of a short run (whole range and a sub-range) -- with fixed seeds; and predict, loo, predict_new_group and
+newgroup_latents at the edges of the predictive kernels' row-tile walk (tile_edges).
 
     python scripts/draw_entries_dump.py --out a.npz                      # this tree's library
     EPX_LIB=/path/to/other/libepx.so python scripts/draw_entries_dump.py --out b.npz
@@ -66,12 +67,57 @@ def entries(eng, tag, out, theta=None, chains=None, k0=0, count=None, seed=0):
     out[tag + '/pooled_sum_only'] = eng.pooled_moments(want_scatter=False, **kw)[1]
 
 
+def tile_edges(out):
+    """The predictive entries at the edges of their row-tile walk (csrc/predict_tile.h): an empty site, a full tile of 16
+    rows, one row past a tile, one past a workgroup's 64; both homes of the LOO tile; a new group's pool of several
+    chunks with a partial last slab."""
+    from epstan_amd.engine import HipEngine, is_gauss
+    K, S = 5, 40
+    for model, D in (('m1b_sg', 3), ('m4b_sg', 3), ('m5b_sg', 3), ('m4a_sg', 3), ('m4b_sg', 128)):
+        tag = 'tile/%s-D%d' % (model, D)
+        rng = np.random.RandomState(500 + D)
+        X, y, k_lim = problem(model, D, [4] * K, 77)
+        eng = HipEngine(model, X, y, k_lim)
+        theta = 0.5 * rng.randn(K, S, eng.P) + 0.3
+
+        def responses(n):
+            return rng.randn(n) if is_gauss(model) else (rng.rand(n) < 0.5).astype(float)
+
+        row_lim = np.concatenate(([0], np.cumsum([3, 0, 16, 17, 65])))
+        Xn = rng.randn(int(row_lim[-1]), D)
+        out[tag + '/predict'] = eng.predict(Xn, row_lim, None, None, theta=theta)
+        out[tag + '/predict_y'] = eng.predict(Xn, row_lim, None, responses(len(Xn)), theta=theta)
+        # four labels: 65 rows, 17, 1 and none; N = 5 x 40 x 3 = 600 members are chunks of 256, 256 and 88 (5.5 slabs)
+        gidx = rng.permutation(np.repeat([0, 1, 3], [65, 17, 1])).astype(np.int32)
+        labels = np.array([5, 11, 2, 40], dtype=np.int32)
+        Xg, yg = rng.randn(len(gidx), D), responses(len(gidx))
+        for R in (1, 3):
+            for name, yy in (('', None), ('_y', yg)):
+                rows, glpd, N = eng.predict_new_group(Xg, gidx, labels, yy, seed=9, t0=3, R=R, theta=theta)
+                out['%s/newgroup%s-R%d' % (tag, name, R)] = rows
+                out['%s/newgroup%s-R%d-glpd' % (tag, name, R)] = glpd
+                out['%s/newgroup%s-R%d-N' % (tag, name, R)] = np.array(N)
+        out[tag + '/latents'] = eng.newgroup_latents(9, 11, 3, 17, 3)
+        eng.close()
+    for model in ('m4b_sg', 'm4a_sg'):
+        X, y, k_lim = problem(model, 3, [7, 16, 17, 65], 78)
+        eng = HipEngine(model, X, y, k_lim)
+        theta = 0.5 * np.random.RandomState(226).randn(4, 226, eng.P) + 0.3
+        for budget in (None, '0', '70000'):              # the LDS tile, the workspace tile, fewer tiles per work item
+            if budget is not None:
+                os.environ['EPX_LOO_LDS_BYTES'] = budget
+            out['tile/%s/loo-lds-%s' % (model, budget)] = eng.loo(theta=theta)
+        del os.environ['EPX_LOO_LDS_BYTES']
+        eng.close()
+
+
 def dump(path):
     from epstan_amd import _lib
     from epstan_amd.engine import HipEngine
     if _lib.device_count() < 1:
         raise SystemExit('draw_entries_dump.py needs a HIP device')
     out = {}
+    tile_edges(out)
     for model in ('m1b_sg', 'm4b_sg', 'm4a_sg'):
         for D, chains, nkeep in SHAPES:
             K = 5
