@@ -141,6 +141,7 @@ SIGNATURES = {
     'epx_get_chain_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p]),
     'epx_rng_probe': (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32,
                                      ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_double_p]),
+    'epx_math_probe': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, c_double_p, c_double_p, c_double_p]),
     'epx_invert_normal_params': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
                                                 c_double_p, ctypes.c_int, c_int32_p]),
     'epx_olse': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int,
@@ -238,6 +239,22 @@ def dptr(a):
         return None
     assert a.dtype == np.float64
     return a.ctypes.data_as(c_double_p)
+
+
+# enum epx_math_probe_kind (include/epx.h), in its order
+MATH_PROBE_KINDS = ('rcp', 'exp', 'exp_vc', 'log1p_unit', 'log_ge1', 'log_ge1_vc', 'log_pos', 'lse2_lean', 'lse2', 'merge',
+                    'terms', 'split', 'split2_a', 'split2_b', 'pair_lean_a', 'pair_lean_b')
+
+
+def math_probe(kind, a, b=None, device=0):
+    """TEST HOOK epx_math_probe: the (n, 4) results of the lean device function `kind` (a name of MATH_PROBE_KINDS) at
+    (a[i], b[i]); b defaults to zeros."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.zeros_like(a) if b is None else np.ascontiguousarray(b, dtype=np.float64)
+    assert a.ndim == 1 and a.shape == b.shape
+    out = np.zeros((a.shape[0], 4))
+    check(load().epx_math_probe(int(device), MATH_PROBE_KINDS.index(kind), a.shape[0], dptr(a), dptr(b), dptr(out)))
+    return out
 
 
 def device_synchronize(device=0):

@@ -1970,3 +1970,24 @@ int epx_rng_probe(int device, uint64_t seed, int chain, uint32_t t, uint32_t kin
     HIPCHK(hipMemcpy(out4, od, 32, hipMemcpyDeviceToHost));
     return 0;
 }
+
+int epx_math_probe(int device, int kind, long long n, const double *a, const double *b, double *out) {
+    DeviceGuard guard;
+    if (need_device(device)) return -1;
+    if (kind < 0 || kind >= EPX_MP_COUNT) return fail("epx_math_probe: unknown kind %d", kind);
+    if (n < 0) return fail("epx_math_probe: n = %lld elements", n);
+    if (n == 0) return 0;
+    if (!a || !b || !out) return fail("epx_math_probe: a, b and out are required");
+    DevBuf<double> ab, od;
+    HIPCHK(ab.alloc((size_t)n * 2));
+    HIPCHK(od.alloc((size_t)n * 4));
+    double *ad = ab, *bd = ad + n;
+    HIPCHK(hipMemcpy(ad, a, (size_t)n * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(bd, b, (size_t)n * 8, hipMemcpyHostToDevice));
+    const long long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_math_probe, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, 0, kind, n, ad, bd, od);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, od, (size_t)n * 4 * 8, hipMemcpyDeviceToHost));
+    return 0;
+}

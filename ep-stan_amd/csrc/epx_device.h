@@ -256,8 +256,11 @@ __device__ inline void merge_weights(double a, double b, double &lse, double &p_
 // ----------------------------------------------------------------------------
 // Lean double-precision elementary functions for the per-leapfrog hot path.
 // The kernel is bound by instruction issue, and the library exp/log1p cost ~250
-// instructions per logistic term (extended-precision internals); these are
-// ~1e-16 relative (checked against the oracle's libm in the gradient tests) in ~60.
+// instructions per logistic term (extended-precision internals); these take ~60 and are good to a few ulps:
+// tests/test_gpu_lean_math.py evaluates each of them on its own on the device (epx_math_probe) against long double
+// and pins the maxima.  Measured there on the device: rcp_d 0.50 ulp, exp_d 0.86 ulp (0.80 units of 2^-1074 where the
+// result is subnormal), log1p_unit_d 2.99 ulp below its fold and 2.1e-16 absolute above it, log_ge1_d 3.00 ulp, the
+// residual y - sigmoid(f) 1.7e-16 absolute, w = 1 + exp(-|f|) 0.87 ulp (the table is in DESIGN.md section 3.1a).
 // v_rcp_f64 is good to 2^-24.4 (scripts/probe/rcp_accuracy.hip, profiles/r06_rcp_f64_accuracy.txt).  One THIRD-order
 // step behind it -- t = 1 - x r, r (1 + t + t^2): truncation t^3 ~ 1e-22 -- takes three FMAs where two Newton steps took
 // four, and rounds as well (round 6; the logistic pair is the row phase's instruction count).
@@ -339,7 +342,10 @@ __device__ inline void logistic_terms(double f, double y, double &ll, double &g)
     const double l1p = log1p_unit_d(e);
     const double inv = rcp_d(1.0 + e);
     const double s = (f >= 0) ? inv : e * inv;
-    ll = y * f - (fmax(f, 0.0) + l1p);
+    // y f - max(f, 0) FIRST: it is exact for y = 0, 1, and the one rounding that is left is that of ll itself.  Written
+    // as y f - (max(f, 0) + l1p) the sum rounds at half an ulp of f before f cancels for y = 1: 16 ulps of 1 at f = 33,
+    // where ll = -4.6e-15 (tests/test_gpu_lean_math.py; as many instructions either way)
+    ll = (y * f - fmax(f, 0.0)) - l1p;
     g = y - s;
 }
 

@@ -457,5 +457,6 @@ struct CarryArgs {
 __global__ void k_carry_update(CarryArgs a);
 __global__ void k_rng_probe(uint64_t seed, int chain, uint32_t t, uint32_t kind, uint32_t a,
                             uint32_t b, double *out4);
+__global__ void k_math_probe(int kind, long long n, const double *a, const double *b, double *out);   // out: n x 4
 
 }  // namespace epx

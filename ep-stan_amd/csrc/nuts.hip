@@ -607,4 +607,36 @@ __global__ void k_rng_probe(uint64_t seed, int chain, uint32_t t, uint32_t kind,
     }
 }
 
+// One function of epx_device.h per element, chosen by `kind` (EPX_MP_*, include/epx.h), on (a[i], b[i]); four results
+// per element, unused slots 0.  The two-slot logistic forms are probed one slot at a time: the other slot gets a fixed
+// finite argument, so that a slot which depended on its neighbour would show against logistic_split.
+__global__ void __launch_bounds__(256)
+k_math_probe(int kind, long long n, const double *a, const double *b, double *out) {
+    const double fd = 0.25, yd = 1.0;                 // the idle slot's logit and response
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const double x = a[i], y = b[i];
+        double o0 = 0.0, o1 = 0.0, o2 = 0.0, o3 = 0.0, u0, u1, u2;
+        switch (kind) {
+        case EPX_MP_RCP:          o0 = rcp_d(x); break;
+        case EPX_MP_EXP:          o0 = exp_d(x); break;
+        case EPX_MP_EXP_VC:       o0 = exp_d_vc(x); break;
+        case EPX_MP_LOG1P_UNIT:   o0 = log1p_unit_d(x); break;
+        case EPX_MP_LOG_GE1:      o0 = log_ge1_d(x); break;
+        case EPX_MP_LOG_GE1_VC:   o0 = log_ge1_d_vc(x); break;
+        case EPX_MP_LOG_POS:      o0 = log_pos_d(x); break;
+        case EPX_MP_LSE2_LEAN:    o0 = log_sum_exp2_lean(x, y); break;
+        case EPX_MP_LSE2:         o0 = log_sum_exp2(x, y); break;
+        case EPX_MP_MERGE:        merge_weights(x, y, o0, o1); break;
+        case EPX_MP_TERMS:        logistic_terms(x, y, o0, o1); break;
+        case EPX_MP_SPLIT:        logistic_split(x, y, o0, o1, o2); break;
+        case EPX_MP_SPLIT2_A:     logistic_split2(x, fd, y, yd, o0, u0, o1, u1, o2, u2); break;
+        case EPX_MP_SPLIT2_B:     logistic_split2(fd, x, yd, y, u0, o0, u1, o1, u2, o2); break;
+        case EPX_MP_PAIR_LEAN_A:  logistic_pair_lean(x, fd, 0.5 - y, 0.5 - yd, o0, u0, o1, u1, o2, u2); break;
+        case EPX_MP_PAIR_LEAN_B:  logistic_pair_lean(fd, x, 0.5 - yd, 0.5 - y, u0, o0, u1, o1, u2, o2); break;
+        default: break;
+        }
+        out[4 * i] = o0; out[4 * i + 1] = o1; out[4 * i + 2] = o2; out[4 * i + 3] = o3;
+    }
+}
+
 }  // namespace epx

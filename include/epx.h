@@ -681,6 +681,19 @@ int epx_get_chain_stats(epx_ctx *ctx, int k0, int count, double *out);
 /* TEST HOOK: uniforms/normals of the device random stream */
 int epx_rng_probe(int device, uint64_t seed, int chain, uint32_t t, uint32_t kind, uint32_t a,
                   uint32_t b, double *out4);
+/* TEST HOOK: the lean elementary functions of the sampler kernels (csrc/epx_device.h), one of them per call, elementwise
+ * on the device: out[4 i .. 4 i + 3] = the function `kind` names at (a[i], b[i]); slots it does not fill are 0.
+ *   one argument a[i], result in slot 0:  RCP rcp_d, EXP exp_d, EXP_VC exp_d_vc, LOG1P_UNIT log1p_unit_d, LOG_GE1
+ *     log_ge1_d, LOG_GE1_VC log_ge1_d_vc, LOG_POS log_pos_d;
+ *   LSE2_LEAN log_sum_exp2_lean(a, b), LSE2 log_sum_exp2(a, b): slot 0;  MERGE merge_weights(a, b): (lse, p_right);
+ *   logit f = a[i], response y = b[i] (0.0 or 1.0):  TERMS logistic_terms: (ll, g);  SPLIT logistic_split: (lin, w, g);
+ *     SPLIT2_A / SPLIT2_B logistic_split2's first / second slot and PAIR_LEAN_A / PAIR_LEAN_B logistic_pair_lean's (which
+ *     takes 1/2 - y): (lin, w, g), the other slot fed a fixed finite argument.
+ * An unknown kind or n < 0 is refused.  No reference counterpart. */
+enum epx_math_probe_kind { EPX_MP_RCP = 0, EPX_MP_EXP, EPX_MP_EXP_VC, EPX_MP_LOG1P_UNIT, EPX_MP_LOG_GE1, EPX_MP_LOG_GE1_VC,
+                           EPX_MP_LOG_POS, EPX_MP_LSE2_LEAN, EPX_MP_LSE2, EPX_MP_MERGE, EPX_MP_TERMS, EPX_MP_SPLIT,
+                           EPX_MP_SPLIT2_A, EPX_MP_SPLIT2_B, EPX_MP_PAIR_LEAN_A, EPX_MP_PAIR_LEAN_B, EPX_MP_COUNT };
+int epx_math_probe(int device, int kind, long long n, const double *a, const double *b, double *out);
 
 /*
  * Stand-alone batched forms of epstan/util.py on device (no context needed):
