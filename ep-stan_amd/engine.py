@@ -27,6 +27,13 @@ MODEL_IDS = {'m1b_sg': 0, 'm2b_sg': 1, 'm3b_sg': 2, 'm4b_sg': 3, 'm5b_sg': 4,
 
 def is_gauss(model):
     return MODEL_IDS[model] >= 5
+
+
+def site_spec(model):
+    """(b-model id, Gaussian family, single-group program) of a site model, as site_params takes them."""
+    return MODEL_IDS[model] % 5, is_gauss(model), model.endswith('_sg')
+
+
 PREC_ESTIM_IDS = {'sample': 0, 'olse': 1}
 QI, QI2, DQI = 0, 1, 2
 INIT_IDS = {'random': 0, '0': 1, 0: 1, 'prev': 2}
@@ -272,8 +279,7 @@ class HipEngine(object):
         them.  The draws and their cavities are those of the last sampling call (`set_draw_reuse(True)` before it), or
         `theta` (count, S, P) with `Om_old` (count, d, d) and `mu_old` (count, d).  Returns (posdef bool[count], rec
         (count, 2): columns reweight.RW_KHAT, RW_WESS, kernel ms)."""
-        count = self.K - k0 if count is None else count
-        theta, S = self._injected(theta, count)
+        count, theta, S = self._draw_range(k0, count, theta)
         if Om_old is not None:
             Om_old = np.asarray(Om_old, dtype=np.float64)
             if Om_old.shape != (count, self.d, self.d):
@@ -503,9 +509,8 @@ class HipEngine(object):
         with n the draws per site and mean / m2 lists, one entry per site, of {name: ndarray} -- the mean and the
         centred sum of squares in the per-site shapes of site_params.named_draws.  The draws are those of the last
         sampling call, on the device; `theta` (count, S, P) injects draws instead (test hook)."""
-        count = self.K - k0 if count is None else count
         names, ids = self._named_ids(names)
-        theta, S = self._injected(theta, count)
+        count, theta, S = self._draw_range(k0, count, theta)
         lens = self._named_lens(ids, self._widest_site())
         L = int(sum(lens))
         mean = np.zeros((count, L))
@@ -541,7 +546,7 @@ class HipEngine(object):
         if row_lim.shape != (count + 1,):
             raise ValueError('row_lim: count + 1 = {} row limits'.format(count + 1))
         Xn, row_group, y = self._new_rows(Xn, int(row_lim[-1]), row_group, 'row_group', y)
-        theta, S = self._injected(theta, count)
+        count, theta, S = self._draw_range(k0, count, theta)
         out = np.zeros((Xn.shape[0], _site_params.PR_COUNT))
         check(self.lib.epx_predict(self.ctx, int(k0), int(count), row_lim.ctypes.data_as(_lib.c_int64_p),
                                    row_group.ctypes.data_as(_lib.c_int32_p) if row_group is not None else None,
@@ -555,11 +560,10 @@ class HipEngine(object):
         the row's new group (None: 0); labels (G): the stream's label of every group; t0: pooled index of site k0's
         first draw.  The draws are those of the last sampling call, on the device; `theta` (count, S, P) injects
         draws instead (test hook)."""
-        count = self.K - k0 if count is None else count
         Xn, gidx, y = self._new_rows(Xn, None, gidx, 'gidx', y)
         n = Xn.shape[0]
         labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
-        theta, S = self._injected(theta, count)
+        count, theta, S = self._draw_range(k0, count, theta)
         G = labels.shape[0]
         out = np.zeros((n, _site_params.PR_COUNT))
         glpd = np.zeros(G)
@@ -585,8 +589,7 @@ class HipEngine(object):
         (rows, 6), columns loo.LO_LPD, LO_LL_MEAN, LO_LL_M2, LO_ELPD, LO_KHAT, LO_WESS, in the context's row order.  The
         draws are those of the last sampling call, on the device; `theta` (count, S, P) injects draws instead (test
         hook).  with_n: also return the draws per site."""
-        count = self.K - k0 if count is None else count
-        theta, S = self._injected(theta, count)
+        count, theta, S = self._draw_range(k0, count, theta)
         ok = 0 <= k0 and count >= 1 and k0 + count <= self.K        # (a bad range: the library says so)
         rows = int(self.k_lim[k0 + count] - self.k_lim[k0]) if ok else 0
         out = np.zeros((rows, _loo.LO_COUNT))
@@ -609,29 +612,24 @@ class HipEngine(object):
         multi-group site's own `site_P[k]` coordinates.  The draws, chains and nkeep are those of the last sampling
         call, on the device; `theta` (count, S, P), chain-major, with `chains` injects draws instead (test hook).
         with_n: also return the used draws per site."""
-        count = self.K - k0 if count is None else count
-        if theta is not None and chains is None:
-            raise ValueError('injected draws need `chains`')
-        theta, S = self._injected(theta, count)
-        out = np.zeros((max(int(count), 0), self.P, _diagnostics.DG_COUNT))
-        n = ctypes.c_int()
-        check(self.lib.epx_draw_diagnostics(self.ctx, int(k0), int(count), dptr(theta), int(S),
-                                            int(chains) if theta is not None else 0, dptr(out), ctypes.byref(n)))
-        return (out, n.value) if with_n else out
+        return self._diagnose(self.lib.epx_draw_diagnostics, _diagnostics.DG_COUNT, k0, count, theta, chains, with_n)
 
     def draw_rank_diagnostics(self, k0=0, count=None, theta=None, chains=None, with_n=False):
         """Rank-normalised diagnostics of the draws of the sites k0..k0+count (epx_draw_rank_diagnostics, include/epx.h):
         (count, P, 5), columns diagnostics.RD_RHAT, RD_RHAT_BULK, RD_RHAT_FOLD, RD_ESS_BULK, RD_ESS_TAIL; NaN behind a
         multi-group site's own `site_P[k]` coordinates.  Draws, `theta`, `chains` and `with_n` as `draw_diagnostics`
         takes them; at most diagnostics.RD_MAX_DRAWS used draws per site."""
-        count = self.K - k0 if count is None else count
+        return self._diagnose(self.lib.epx_draw_rank_diagnostics, _diagnostics.RD_COUNT, k0, count, theta, chains, with_n)
+
+    def _diagnose(self, entry, width, k0, count, theta, chains, with_n):
+        """The (count, P, width) records of one of the library's two diagnostics entries (and the used draws per site)."""
         if theta is not None and chains is None:
             raise ValueError('injected draws need `chains`')
-        theta, S = self._injected(theta, count)
-        out = np.zeros((max(int(count), 0), self.P, _diagnostics.RD_COUNT))
+        count, theta, S = self._draw_range(k0, count, theta)
+        out = np.zeros((max(int(count), 0), self.P, width))
         n = ctypes.c_int()
-        check(self.lib.epx_draw_rank_diagnostics(self.ctx, int(k0), int(count), dptr(theta), int(S),
-                                                 int(chains) if theta is not None else 0, dptr(out), ctypes.byref(n)))
+        check(entry(self.ctx, int(k0), int(count), dptr(theta), int(S), int(chains) if theta is not None else 0, dptr(out),
+                    ctypes.byref(n)))
         return (out, n.value) if with_n else out
 
     def rank_normalize(self, x, fold=False):
@@ -650,9 +648,8 @@ class HipEngine(object):
         with n the number of draws, sum (d) = sum (x - center) and scatter (d, d) = sum (x - center)(x - center)', None
         without `want_scatter`; `center` None = 0.  The draws are those of the last sampling call, on the device;
         `theta` (count, S, P) injects draws instead (test hook)."""
-        count = self.K - k0 if count is None else count
         d = self.d
-        theta, S = self._injected(theta, count)
+        count, theta, S = self._draw_range(k0, count, theta)
         if center is not None:
             center = np.ascontiguousarray(center, dtype=np.float64)
             if center.shape != (d,):
@@ -687,7 +684,7 @@ class HipEngine(object):
     def _cut_sites(self, names, lens, rows, k0, lead=()):
         """rows (count,) + lead + (L,), every site's names side by side at the widest site's lengths `lens` -> a list, one
         entry per site, of {name: lead + the per-site shape of site_params.named_draws}."""
-        mid, gauss, sg = MODEL_IDS[self.model] % 5, is_gauss(self.model), self.model.endswith('_sg')
+        mid, gauss, sg = site_spec(self.model)
         off = np.concatenate(([0], np.cumsum(lens)))
         sites, cuts = [], {}                             # cuts: per group count, (name, first, last, shape) of every name
         for b in range(rows.shape[0]):
@@ -701,14 +698,16 @@ class HipEngine(object):
                               for name, lo, hi, shape in cuts[ng]))
         return sites
 
-    def _injected(self, theta, count):
-        """`theta` (count, S, P) as the library takes it, and S; (None, 0): the draws of the last sampling call."""
+    def _draw_range(self, k0, count, theta):
+        """What every entry over draws opens with: (count, theta, S).  count None: the sites from k0 on; `theta` (count, S,
+        P) as the library takes it, and S; (None, 0): the draws of the last sampling call."""
+        count = self.K - k0 if count is None else count
         if theta is None:
-            return None, 0
+            return count, None, 0
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         if theta.ndim != 3 or theta.shape[0] != count or theta.shape[2] != self.P:
             raise ValueError('theta: (count, S, P) = ({}, S, {})'.format(count, self.P))
-        return theta, theta.shape[1]
+        return count, theta, theta.shape[1]
 
     def named_order_stats(self, names, ranks, k0=0, count=None, theta=None):
         """Per-site order statistics of named parameters of the site model (epx_named_order_stats, include/epx.h): a list,
@@ -716,10 +715,9 @@ class HipEngine(object):
         the 0-based ranks r (ascending, distinct, below the draws per site, at most 32), NaN for an element with a NaN
         draw.  The draws are those of the last sampling call, on the device; `theta` (count, S, P) injects draws instead
         (test hook)."""
-        count = self.K - k0 if count is None else count
         names, ids = self._named_ids(names)
         ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
-        theta, S = self._injected(theta, count)
+        count, theta, S = self._draw_range(k0, count, theta)
         lens = self._named_lens(ids, self._widest_site())
         L, R = int(sum(lens)), int(ranks.size)
         out = np.zeros((max(int(count), 0), L, R))
@@ -733,9 +731,8 @@ class HipEngine(object):
         n), L = the elements of `names` in the order given, which every site of the range has to hold alike.  prefix
         (L, n_targets) uint64, not read at shift 56 (None).  The draws are those of the last sampling call, on the device;
         `theta` (count, S, P) injects draws instead (test hook)."""
-        count = self.K - k0 if count is None else count
         names, ids = self._named_ids(names)
-        theta, S = self._injected(theta, count)
+        count, theta, S = self._draw_range(k0, count, theta)
         L, T = int(sum(self._named_lens(ids, k0))), int(n_targets)
         if prefix is not None:
             prefix = np.ascontiguousarray(prefix, dtype=np.uint64)

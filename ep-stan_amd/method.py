@@ -33,9 +33,9 @@ from numpy.linalg import LinAlgError
 from . import diagnostics as _diagnostics
 from . import dispatch as _dispatch
 from . import dist as _dist
+from . import draw_queries as _dq
 from . import engine as _engine
 from . import loo as _loo
-from . import mix_pred as _mix_pred
 from . import newgroup as _newgroup
 from . import quantiles as _quantiles
 from . import reweight as _reweight
@@ -213,9 +213,8 @@ class Worker(object):
         eng = self._eng
         theta = eng.get_draws(self._k, all_params=True)
         ng = 1 if eng.g_cnt is None else int(eng.g_cnt[self._k])
-        mid = _engine.MODEL_IDS[eng.model] % 5
-        self.saved_samp = _site_params.named_draws(
-            mid, eng.D, ng, _engine.is_gauss(eng.model), eng.model.endswith('_sg'), theta, list(names))
+        mid, gauss, sg = _engine.site_spec(eng.model)
+        self.saved_samp = _site_params.named_draws(mid, eng.D, ng, gauss, sg, theta, list(names))
 
     def tilted(self, dQi, dri, save_samples=None, seed=None):
         """Estimate the tilted distribution and write the site parameter update
@@ -591,6 +590,10 @@ class Master(object):
         if self.engine.d != self.dphi:
             raise ValueError("Arg. `dphi`/`prior` ({}) does not match site model {} (dphi {})"
                              .format(self.dphi, self.model_name, self.engine.d))
+        # the draw queries: the engine's own methods, the host route for those it does not have
+        self._queries = _dq.Queries(_dq.HostDraws(
+            lambda: self.engine, self._site_spec(), self.D, self._site_ng[self.k_lo:self.k_hi], self.X[r0w:r1w], self.y[r0w:r1w],
+            np.asarray(self.A_n['j_ind'])[r0w:r1w] if groups else None, k_lim_local, w_stan['chains']))
         if hasattr(self.comm, 'bind'):
             self.comm.bind(self.engine)                   # RCCL communicator of the engine's context (collective)
         # the fused update (epx_update_trial) needs the engine's own communicator (or one rank)
@@ -723,63 +726,7 @@ class Master(object):
 
     def _site_spec(self):
         """(b-model id, Gaussian family, single-group program) of the site model, as site_params takes them."""
-        name = self.model_name
-        return _engine.MODEL_IDS[name] % 5, _engine.is_gauss(name), name.endswith('_sg')
-
-    def _local_named_moments(self, names):
-        """(n, mean, m2) of the named parameters for this rank's sites: lists of {name: ndarray} (see
-        HipEngine.named_moments).  The device engine computes them next to the draws; an engine without
-        `named_moments` (the CPU oracle the tests inject) hands its draws to site_params.named_moments_host."""
-        eng = self.engine
-        if hasattr(eng, 'named_moments'):
-            return eng.named_moments(names)
-        mid, gauss, sg = self._site_spec()
-        n, means, m2s = 0, [], []
-        for j in range(self.K_local):
-            theta = eng.get_draws(j, all_params=True)
-            n, m, v = _site_params.named_moments_host(mid, self.D, int(self._site_ng[self.k_lo + j]), gauss, sg,
-                                                      theta, names)
-            means.append(m)
-            m2s.append(v)
-        return n, means, m2s
-
-    def _gather_site_records(self, names, local, R, head=None):
-        """Records of named parameters of ALL sites on every rank from this rank's: `local` holds one {name: (R,) + the
-        per-site shape} per local site, the result one per site.  One record per site -- its R rows of the site's
-        elements side by side, flattened, padded to the widest site -- is gathered like the site arrays.  head: a number
-        of this rank that travels in front of each of its records; then (sites, heads (K)) is returned."""
-        K, h = self.K, 0 if head is None else 1
-        mid, gauss, sg = self._site_spec()
-        shapes = [[_site_params.named_shape(mid, self.D, int(self._site_ng[k]), gauss, sg, name) for name in names]
-                  for k in range(K)]
-        sizes = [[int(np.prod(sh, dtype=np.int64)) for sh in row] for row in shapes]
-        W = max(sum(row) for row in sizes)
-        rec = np.zeros((h + R * W, self.K_local), order='F')
-        if h:
-            rec[0, :] = head
-        for j in range(self.K_local):
-            flat = np.concatenate([local[j][name].reshape(R, -1) for name in names], axis=1)      # (R, the site's elements)
-            rec[h:, j].reshape(R, W)[:, :flat.shape[1]] = flat
-        full = self.comm.allgather_sites(rec, K)
-        sites = []
-        for k in range(K):
-            rows, d, at = np.ascontiguousarray(full[h:, k]).reshape(R, W), {}, 0
-            for name, sh, size in zip(names, shapes[k], sizes[k]):
-                d[name] = rows[:, at:at + size].reshape((R,) + tuple(sh))
-                at += size
-            sites.append(d)
-        return (sites, full[0, :]) if h else sites
-
-    def _gather_named(self, names, n, means, m2s):
-        """Per-site records of ALL sites on every rank: ns (K), and lists of {name: ndarray}.  The record of a site is
-        [n | means | M2s]: two rows behind the draws per site."""
-        if self.comm.world == 1:
-            return np.full(self.K, n, dtype=np.int64), means, m2s
-        local = [dict((name, np.stack([np.asarray(m[name]), np.asarray(v[name])])) for name in names)
-                 for m, v in zip(means, m2s)]
-        both, ns = self._gather_site_records(names, local, 2, head=n)
-        return (np.rint(ns).astype(np.int64), [dict((name, d[name][0]) for name in names) for d in both],
-                [dict((name, d[name][1]) for name in names) for d in both])
+        return _engine.site_spec(self.model_name)
 
     def mix_pred(self, params, smap=None, param_shapes=None):
         """Mean and variance of named parameters of the site model from the tilted draws of the last iteration
@@ -798,57 +745,12 @@ class Master(object):
         if only_one_param:
             params, smap, param_shapes = [params], [smap], [param_shapes]
         params = list(params)
-        ns, ms, vs = self._gather_named(params, *self._local_named_moments(params))
-        mean, var = [], []
-        for ip, par in enumerate(params):
-            m, v = _mix_pred.combine_moments(
-                ns, [rec[par] for rec in ms], [rec[par] for rec in vs],
-                smap[ip] if smap is not None else None, param_shapes[ip] if param_shapes is not None else None)
-            mean.append(m)
-            var.append(v)
+        ns, ms, vs = _dq.gather_named_moments(self.comm, params, (self._site_spec(), self.D, self._site_ng),
+                                              *self._queries.named_moments(params))
+        mean, var = _dq.mix_moments(ns, ms, vs, params, smap, param_shapes)
         if only_one_param:
             return mean[0], var[0]
         return mean, var
-
-    def _local_named_draws(self, names, j):
-        """{name: draws} of local site j through site_params.named_draws (the host route of an engine without the
-        device methods)."""
-        mid, gauss, sg = self._site_spec()
-        theta = np.ascontiguousarray(self.engine.get_draws(j, all_params=True))
-        return _site_params.named_draws(mid, self.D, int(self._site_ng[self.k_lo + j]), gauss, sg, theta, names)
-
-    def _pooled_order_stats(self, names, shapes, ranks):
-        """{name: (len(ranks),) + shape}: order statistics of the pool of ALL sites' draws of parameters every site holds,
-        selected by counting over all ranks (quantiles.select_pooled)."""
-        eng, T = self.engine, len(ranks)
-        if hasattr(eng, 'pooled_count_pass'):
-            def count_pass(shift, prefix):
-                return eng.pooled_count_pass(names, shift, prefix, T)
-        else:
-            x = np.concatenate([np.concatenate([d[name].reshape(d[name].shape[0], -1) for name in names], axis=1)
-                                for d in (self._local_named_draws(names, j) for j in range(self.K_local))])
-
-            def count_pass(shift, prefix):
-                return _quantiles.count_pass_host(x, shift, prefix, T)
-        values, _, _ = _quantiles.select_pooled(count_pass, self.comm.allreduce_sum, ranks)
-        out, at = {}, 0
-        for name, sh in zip(names, shapes):
-            size = int(np.prod(sh, dtype=np.int64))
-            out[name] = np.ascontiguousarray(values[at:at + size].T).reshape((T,) + tuple(sh))
-            at += size
-        return out
-
-    def _site_order_stats(self, names, ranks):
-        """Per-site order statistics of ALL sites on every rank: a list of {name: (len(ranks),) + per-site shape}.  Every
-        rank selects its own sites' (HipEngine.named_order_stats, or quantiles.site_order_stats_host on an engine
-        without it); one record per site, flattened and padded to the widest site, is gathered like the site arrays."""
-        eng = self.engine
-        if hasattr(eng, 'named_order_stats'):
-            local = eng.named_order_stats(names, ranks)
-        else:
-            local = [dict((name, _quantiles.order_stats(d[name], ranks)) for name in names)
-                     for d in (self._local_named_draws(names, j) for j in range(self.K_local))]
-        return local if self.comm.world == 1 else self._gather_site_records(names, local, len(ranks))
 
     def mix_quantiles(self, params, probs=(0.025, 0.25, 0.5, 0.75, 0.975), smap=None, param_shapes=None):
         """Quantiles of named parameters of the site model from the tilted draws of the last iteration: the credible
@@ -876,20 +778,13 @@ class Master(object):
         params = list(params)
         maps = [smap[ip] if smap is not None else None for ip in range(len(params))]
         S = int(self.engine.get_tilted(0)[2])               # draws per site (the same for every site)
-        mid, gauss, sg = self._site_spec()
+        sites = (self._site_spec(), self.D, self._site_ng)
         result = [None] * len(params)
 
         pooled = [par for par, mp in zip(params, maps) if mp is None]
         if pooled:
             ranks, plan = _quantiles.rank_plan(S * self.K, probs)
-            shapes = []
-            for par in pooled:
-                every = set(_site_params.named_shape(mid, self.D, int(ng), gauss, sg, par) for ng in self._site_ng)
-                if len(every) != 1:
-                    raise ValueError("Without `smap` every site has to hold the whole parameter; the sites' records of "
-                                     "{!r} have the shapes {}".format(par, sorted(every)))
-                shapes.append(every.pop())
-            stats = self._pooled_order_stats(pooled, shapes, ranks)
+            stats = _dq.pooled_order_stats(self._queries, self.comm, pooled, _dq.pooled_shapes(*sites, pooled), ranks)
             for ip, par in enumerate(params):
                 if maps[ip] is None:
                     result[ip] = _quantiles.interpolate(stats[par], ranks, plan)
@@ -899,83 +794,13 @@ class Master(object):
             ranks, plan = _quantiles.rank_plan(S, probs)
             if param_shapes is None or any(param_shapes[ip] is None for ip in range(len(params)) if maps[ip] is not None):
                 raise ValueError("Arg. `param_shapes` has to be given with `smap`")
-            stats = self._site_order_stats(mapped, ranks)
+            stats = _dq.site_order_stats(self._queries, self.comm, mapped, sites, ranks)
             for ip, par in enumerate(params):
-                mp = maps[ip]
-                if mp is None:
-                    continue
-                if len(mp) != self.K:
-                    raise ValueError("Arg. `smap` of {!r} needs one index per site ({}), it has {}".format(
-                        par, self.K, len(mp)))
-                filled = np.zeros(param_shapes[ip], dtype=np.int64)
-                shape = filled.shape
-                q = np.full((len(plan),) + shape, np.nan)
-                for k in range(self.K):
-                    qk = _quantiles.interpolate(stats[k][par], ranks, plan)
-                    if qk.shape[1:] != np.shape(filled[mp[k]]):
-                        raise ValueError("The record of site {} has shape {}, its map addresses {} of the parameter {}"
-                                         .format(k, qk.shape[1:], np.shape(filled[mp[k]]), shape))
-                    filled[mp[k]] += 1
-                    for ir in range(len(plan)):
-                        q[ir][mp[k]] = qk[ir]
-                if np.any(filled == 0):
-                    raise ValueError("Arg. `smap` does not fill the parameter {!r}".format(par))
-                if np.any(filled > 1):
-                    raise ValueError("Arg. `smap` lets several sites fill one index of {!r}: the quantile of a pool of "
-                                     "sites is not a function of the sites' quantiles".format(par))
-                result[ip] = q
+                if maps[ip] is not None:
+                    result[ip] = _dq.place_site_quantiles(par, stats, ranks, plan, maps[ip], param_shapes[ip])
         if only_one_param:
             return result[0]
         return result
-
-    def _new_rows(self, X_new):
-        """`X_new` of predict / predict_new_group as float64 (n, D)."""
-        X_new = np.asarray(X_new, dtype=np.float64)
-        if X_new.ndim != 2 or X_new.shape[1] != self.D:
-            raise ValueError("Argument `X_new` should be two dimensional with {} columns".format(self.D))
-        return X_new
-
-    def _new_responses(self, y_new, n, finite):
-        """`y_new` of predict / predict_new_group as contiguous float64 (n,), or None.  The Bernoulli models take 0 or
-        1; the Gaussian ones anything, or with `finite` (a new group's joint term adds its rows' terms up) finite
-        values only."""
-        if y_new is None:
-            return None
-        ys = np.ascontiguousarray(y_new, dtype=np.float64)
-        if ys.shape != (n,):
-            raise ValueError("The shapes of `y_new` and `X_new` does not match")
-        gauss = self._site_spec()[1]
-        if gauss and not finite:
-            return ys
-        bad = np.nonzero(~np.isfinite(ys) if gauss else (ys != 0) & (ys != 1))[0]
-        if bad.size:
-            raise ValueError("`y_new` of row {}: {}; site model {!r} takes {}".format(
-                int(bad[0]), ys[bad[0]], self.model_name, "finite responses" if gauss else "responses 0 or 1"))
-        return ys
-
-    @staticmethod
-    def _predictive_result(rec, has_y, n, **more):
-        """The result of predict / predict_new_group from the records `rec` (rows, 4) over n draws or pool members."""
-        return dict(mean=rec[:, _site_params.PR_MEAN].copy(), f_mean=rec[:, _site_params.PR_F_MEAN].copy(),
-                    f_var=rec[:, _site_params.PR_F_M2] / (n - 1),
-                    lpd=rec[:, _site_params.PR_LPD].copy() if has_y else None, **more, n=n)
-
-    def _local_predict(self, Xn, row_lim, group, y):
-        """Prediction records (n_local, 4) of new rows of this rank's sites (see HipEngine.predict).  The device engine
-        computes them next to the draws; an engine without `predict` (the CPU oracle the tests inject) hands its draws
-        to site_params.predict_host."""
-        eng = self.engine
-        if hasattr(eng, 'predict'):
-            return eng.predict(Xn, row_lim, group, y)
-        mid, gauss, _ = self._site_spec()
-        out = np.zeros((Xn.shape[0], _site_params.PR_COUNT))
-        for j in range(self.K_local):
-            lo, hi = int(row_lim[j]), int(row_lim[j + 1])
-            if hi > lo:
-                out[lo:hi] = _site_params.predict_host(
-                    mid, self.D, int(self._site_ng[self.k_lo + j]), gauss, eng.get_draws(j, all_params=True), Xn[lo:hi],
-                    None if group is None else group[lo:hi], None if y is None else y[lo:hi])
-        return out
 
     def predict(self, X_new, site_sizes=None, site_ind=None, j_ind=None, y_new=None):
         """Posterior predictive of new rows from the tilted draws of the last iteration: what the fitted site models
@@ -996,68 +821,21 @@ class Master(object):
         self._need_draws("predict", "nothing can be predicted from them")
         if (site_sizes is None) == (site_ind is None):
             raise ValueError("Give exactly one of `site_sizes` and `site_ind`")
-        X_new = self._new_rows(X_new)
-        n, K = X_new.shape[0], self.K
-        order = None
-        if site_sizes is not None:
-            cnt = np.asarray(site_sizes, dtype=np.int64)
-            if cnt.shape != (K,) or np.any(cnt < 0) or cnt.sum() != n:
-                raise ValueError("`site_sizes`: {} non-negative counts that add up to the rows of `X_new`".format(K))
-        else:
-            site_ind = np.asarray(site_ind)
-            if site_ind.shape != (n,) or not np.issubdtype(site_ind.dtype, np.integer) \
-                    or (n and (site_ind.min() < 0 or site_ind.max() >= K)):
-                raise ValueError("`site_ind`: one site index in [0, {}) per row of `X_new`".format(K))
-            order = np.argsort(site_ind, kind='mergesort')       # stable: rows keep their order inside a site
-            cnt = np.bincount(site_ind, minlength=K).astype(np.int64)
-        lim = np.concatenate(([0], np.cumsum(cnt)))
-        rows = np.arange(n) if order is None else order          # caller's row of every sorted row
-        mid, gauss, sg = self._site_spec()
-        group = None
-        if sg:
-            if j_ind is not None:
-                raise ValueError("site model {!r} holds one group per site: it takes no `j_ind`".format(self.model_name))
-        else:
-            if j_ind is None:
-                raise ValueError("site model {!r} holds several groups per site: give the 1-based group of every "
-                                 "new row within its site as `j_ind`".format(self.model_name))
-            j_ind = np.asarray(j_ind)
-            if j_ind.shape != (n,) or not np.issubdtype(j_ind.dtype, np.integer):
-                raise ValueError("`j_ind`: one integer per row of `X_new`")
-            group = (j_ind[rows] - 1).astype(np.int32)
-            bad = np.nonzero((group < 0) | (group >= np.repeat(self._site_ng, cnt)))[0]
-            if bad.size:
-                i = int(bad[0])
-                k = int(np.searchsorted(lim, i, side='right') - 1)
-                raise ValueError("`j_ind` of row {}: group {} outside 1..{} of site {}"
-                                 .format(int(rows[i]), int(group[i]) + 1, int(self._site_ng[k]), k))
-        ys = self._new_responses(y_new, n, finite=False)
+        X_new = _dq.new_rows(X_new, self.D)
+        n = X_new.shape[0]
+        _, gauss, sg = self._site_spec()
+        rows, lim, group = _dq.plan_rows(n, self.K, site_sizes, site_ind, j_ind, self._site_ng, sg, self.model_name)
+        ys = _dq.new_responses(y_new, n, gauss, False, self.model_name)
         if ys is not None:
             ys = np.ascontiguousarray(ys[rows])
         Xs = np.ascontiguousarray(X_new[rows])
         lo, hi = int(lim[self.k_lo]), int(lim[self.k_hi])
-        rec = np.zeros((n, _site_params.PR_COUNT))
-        rec[lo:hi] = self._local_predict(Xs[lo:hi], lim[self.k_lo:self.k_hi + 1] - lo,
-                                         None if group is None else group[lo:hi], None if ys is None else ys[lo:hi])
-        if ys is None:
-            rec[:, _site_params.PR_LPD] = 0.0                    # (NaN without responses: nothing to add up)
-        if n:
-            rec = self.comm.allreduce_sum(rec)
+        local = self._queries.predict(Xs[lo:hi], lim[self.k_lo:self.k_hi + 1] - lo,
+                                      None if group is None else group[lo:hi], None if ys is None else ys[lo:hi])
+        rec = _dq.sum_predict_rows(self.comm, local, lo, hi, n, ys is not None)
         out = np.empty_like(rec)
         out[rows] = rec
-        return self._predictive_result(out, ys is not None, self.engine.num_draws())
-
-    def _local_predict_new_group(self, Xn, gidx, labels, y, seed, R):
-        """(rows (n, 4), glpd (G,), N) of new groups against this rank's sites' draws (see HipEngine.predict_new_group).
-        The device engine computes them next to the draws; an engine without `predict_new_group` (the CPU oracle the
-        tests inject) hands the phi of its draws to newgroup.predict_new_group_host."""
-        eng = self.engine
-        t0 = self.k_lo * eng.num_draws()
-        if hasattr(eng, 'predict_new_group'):
-            return eng.predict_new_group(Xn, gidx, labels, y, seed=seed, t0=t0, R=R)
-        mid, gauss, _ = self._site_spec()
-        phi = np.stack([np.ascontiguousarray(eng.get_draws(j)) for j in range(self.K_local)])
-        return _newgroup.predict_new_group_host(mid, self.D, gauss, phi, Xn, gidx, labels, y, seed, t0, R)
+        return _dq.predictive_result(out, ys is not None, self.engine.num_draws())
 
     def predict_new_group(self, X_new, group=None, y_new=None, R=1, seed=0):
         """Posterior predictive of rows of groups that were NOT in the data, from the tilted draws of the last iteration
@@ -1077,7 +855,7 @@ class Master(object):
         several ranks every rank runs all rows against its own sites' draws, and one collective of a rank-slotted
         record followed by newgroup.merge in rank order makes every rank return the same result."""
         self._need_draws("predict a new group", "nothing can be predicted from them")
-        X_new = self._new_rows(X_new)
+        X_new = _dq.new_rows(X_new, self.D)
         n = X_new.shape[0]
         if group is None:
             group = np.zeros(n, dtype=np.int64)
@@ -1091,47 +869,16 @@ class Master(object):
             raise ValueError("`R`: an integer number of replicates in 1..{}".format(_newgroup.R_MAX))
         if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
             raise ValueError("`seed`: an integer in [0, 2^64)")
-        ys = self._new_responses(y_new, n, finite=True)
+        ys = _dq.new_responses(y_new, n, self._site_spec()[1], True, self.model_name)
         S = self.engine.num_draws()
         if self.K * S > 2 ** 32:
             raise ValueError("{} sites x {} draws: more than 2^32 pooled draws".format(self.K, S))
         labels, gidx = np.unique(group, return_inverse=True)
-        G = labels.shape[0]
-        rows, glpd, N = self._local_predict_new_group(np.ascontiguousarray(X_new), gidx.astype(np.int32), labels, ys,
-                                                      int(seed), int(R))
-        world = self.comm.world
-        if world > 1:
-            # every rank's record in its own slot, one sum, the pools merged in rank order
-            width = n * _site_params.PR_COUNT + G + 1
-            rec = np.zeros((world, width))
-            mine = np.concatenate((rows.reshape(-1), glpd, [float(N)]))
-            rec[self.comm.rank] = np.where(np.isnan(mine), 0.0, mine) if ys is None else mine
-            rec = np.asarray(self.comm.allreduce_sum(rec.reshape(-1))).reshape(world, width)
-            parts = [(rec[r, :n * _site_params.PR_COUNT].reshape(n, _site_params.PR_COUNT),
-                      rec[r, n * _site_params.PR_COUNT:-1], int(round(rec[r, -1]))) for r in range(world)]
-            rows, glpd, N = _newgroup.merge(parts)
-        return self._predictive_result(rows, ys is not None, N, groups=labels.astype(np.int64),
-                                       group_lpd=np.array(glpd) if ys is not None else None)
-
-    def _local_loo(self):
-        """Leave-one-out records (rows of this rank's sites, 6) and the draws per site (see HipEngine.loo).  The device
-        engine computes them next to the draws; an engine without `loo` (the CPU oracle the tests inject) hands its
-        draws to loo.loo_host."""
-        eng = self.engine
-        if hasattr(eng, 'loo'):
-            return eng.loo(with_n=True)
-        mid, gauss, sg = self._site_spec()
-        r0 = int(self.k_lim[self.k_lo])
-        out = np.zeros((int(self.k_lim[self.k_hi]) - r0, _loo.LO_COUNT))
-        j_ind = None if sg else np.asarray(self.A_n['j_ind'])
-        S = 0
-        for j in range(self.K_local):
-            lo, hi = int(self.k_lim[self.k_lo + j]), int(self.k_lim[self.k_lo + j + 1])
-            theta = eng.get_draws(j, all_params=True)
-            S = theta.shape[0]
-            out[lo - r0:hi - r0] = _loo.loo_host(mid, self.D, int(self._site_ng[self.k_lo + j]), gauss, theta,
-                                                 self.X[lo:hi], None if sg else j_ind[lo:hi] - 1, self.y[lo:hi])
-        return out, S
+        rows, glpd, N = self._queries.predict_new_group(np.ascontiguousarray(X_new), gidx.astype(np.int32), labels, ys,
+                                                        seed=int(seed), t0=self.k_lo * S, R=int(R))
+        rows, glpd, N = _dq.merge_new_group(self.comm, rows, glpd, N, ys is not None)
+        return _dq.predictive_result(rows, ys is not None, N, groups=labels.astype(np.int64),
+                                     group_lpd=np.array(glpd) if ys is not None else None)
 
     def loo(self):
         """Leave-one-out cross-validation of the fitted site models on the rows they were fitted to, from the tilted
@@ -1158,19 +905,8 @@ class Master(object):
         on the matrix pipe, keeps them on chip and reduces them to six numbers per row.  With several ranks every
         rank computes the rows of its own sites and one all-reduce makes every rank return the same result."""
         self._need_draws("cross-validate", "nothing can be cross-validated from them")
-        lo, hi = int(self.k_lim[self.k_lo]), int(self.k_lim[self.k_hi])
-        loc, S = self._local_loo()
-        rec = loc
-        if self.comm.world > 1:
-            # a sum carries neither NaN (a row with a non-finite log-likelihood) nor +inf (KHAT of a row that was not
-            # smoothed) next to the other ranks' zeros: they travel as a code beside the (N, 6) records
-            both = np.zeros((self.N, 2 * _loo.LO_COUNT))
-            both[lo:hi, :_loo.LO_COUNT] = np.where(np.isfinite(loc), loc, 0.0)
-            both[lo:hi, _loo.LO_COUNT:] = np.where(np.isnan(loc), 1.0, np.where(loc == np.inf, 2.0,
-                                                                                 np.where(loc == -np.inf, 3.0, 0.0)))
-            both = self.comm.allreduce_sum(both)
-            rec, code = both[:, :_loo.LO_COUNT], both[:, _loo.LO_COUNT:]
-            rec = np.where(code == 1.0, np.nan, np.where(code == 2.0, np.inf, np.where(code == 3.0, -np.inf, rec)))
+        loc, S = self._queries.loo(with_n=True)
+        rec = _dq.sum_loo_rows(self.comm, loc, int(self.k_lim[self.k_lo]), int(self.k_lim[self.k_hi]), self.N)
         return _loo.summarise(rec, S, self.k_lim)
 
     def diagnostics(self, rank=False):
@@ -1198,43 +934,14 @@ class Master(object):
         chains that agree in location and differ in scale, which `rhat` does not; the tail ESS measures the draws the
         second moments, and so the precision estimate, rest on.  The other entries are those of rank=False."""
         self._need_draws("diagnose draws", "nothing can be diagnosed from them")
-        eng, C = self.engine, _diagnostics.DG_COUNT
-        chains = int(self.workers[self.k_lo].stan_params['chains'])
-        ng_local = self._site_ng[self.k_lo:self.k_hi]
-        pg = (eng.P - eng.d) // int(ng_local.max())              # coordinates per group behind phi
-        site_P = eng.d + self._site_ng * pg                      # (K): every site's own coordinates
-        Pmax = int(site_P.max())
-        rec = np.full((Pmax * C + 1, self.K_local), np.nan, order='F')
-
-        def on_the_host(record_of, width):                       # (K_local, P, width) records and the used draws
-            loc = np.full((self.K_local, eng.P, width), np.nan)
-            for j in range(self.K_local):
-                Pk = int(site_P[self.k_lo + j])
-                theta = np.ascontiguousarray(eng.get_draws(j, all_params=True))
-                loc[j, :Pk] = record_of(theta[:, :Pk], chains)
-            return loc, 2 * chains * ((theta.shape[0] // chains) // 2)
-
-        if hasattr(eng, 'draw_diagnostics'):
-            loc, n = eng.draw_diagnostics(with_n=True)
-        else:
-            loc, n = on_the_host(_diagnostics.diagnostics_host, C)
-        for j in range(self.K_local):
-            rec[:eng.P * C, j] = loc[j].ravel()
-        rec[-1, :] = n
-        full = self.comm.allgather_sites(rec, self.K)
-        out = np.ascontiguousarray(full[:-1, :].T).reshape(self.K, Pmax, C)
+        eng = self.engine
+        pg = (eng.P - eng.d) // int(self._site_ng[self.k_lo:self.k_hi].max())     # coordinates per group behind phi
+        site_P = eng.d + self._site_ng * pg                                       # (K): every site's own coordinates
+        out, ns = _dq.gather_diagnostics(self.comm, site_P, *self._queries.draw_diagnostics(with_n=True))
         rank_out = None
         if rank:
-            R = _diagnostics.RD_COUNT
-            if hasattr(eng, 'draw_rank_diagnostics'):
-                loc = eng.draw_rank_diagnostics()
-            else:
-                loc, _ = on_the_host(_diagnostics.rank_diagnostics_host, R)
-            rrec = np.full((Pmax * R, self.K_local), np.nan, order='F')
-            for j in range(self.K_local):
-                rrec[:eng.P * R, j] = loc[j].ravel()
-            rank_out = np.ascontiguousarray(self.comm.allgather_sites(rrec, self.K).T).reshape(self.K, Pmax, R)
-        return _diagnostics.summarise(out, np.rint(full[-1, :]).astype(np.int64), rank_out)
+            rank_out, _ = _dq.gather_diagnostics(self.comm, site_P, self._queries.draw_rank_diagnostics())
+        return _diagnostics.summarise(out, np.rint(ns).astype(np.int64), rank_out)
 
     # ---- dispatch of the sampling launches: the policy is dispatch.py's, these are its two knobs and what it needs to
     # know of this rank
