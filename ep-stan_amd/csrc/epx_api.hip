@@ -1569,6 +1569,66 @@ int epx_loo(epx_ctx *c, int k0, int count, const double *theta, int S, double *o
     return sync.finish();
 }
 
+int epx_ppc(epx_ctx *c, int k0, int count, uint64_t seed, long long row0, const double *theta, int S, double *out_groups,
+            double *out_sites, double *out_draws, int *nsamp) {
+    CTX(c);
+    if (check_range(c, k0, count)) return -1;
+    if (c->D > EPX_PR_DMAX) return fail("epx_ppc: D = %d columns, at most %d", c->D, (int)EPX_PR_DMAX);
+    if (!out_groups) return fail("epx_ppc: out_groups is required");
+    if (c->N > 0x7fffffff) return fail("epx_ppc: %lld rows, at most 2^31 - 1", (long long)c->N);
+    if (row0 < 0 || row0 + (long long)c->k_lim[k0 + count] >= (1ll << 32))
+        return fail("epx_ppc: row0 = %lld puts the rows of the call at [%lld,%lld), outside [0,2^32 - 1)", row0,
+                    row0 + (long long)c->k_lim[k0], row0 + (long long)c->k_lim[k0 + count]);
+    PpcArgs a;
+    DrawSource src;
+    if (draw_source(c, "epx_ppc", k0, count, theta, S, nullptr, &src)) return -1;
+    S = src.S;
+    if (nsamp) *nsamp = S;
+    a.p.m = predict_model(c); a.p.S = S;
+    if (S > ppc_max_draws(a.p.m.KP))
+        return fail("epx_ppc: S = %d draws, at most %d (a group's 3 x S per-draw sums are kept in LDS)", S,
+                    ppc_max_draws(a.p.m.KP));
+    a.p.k0 = k0; a.p.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    a.p.perm = nullptr; a.p.y = nullptr; a.p.out = nullptr; a.p.X = c->X;
+    a.y8 = c->y; a.yd = c->yd;
+    a.seed = seed; a.row0 = row0; a.count = count;
+    // work items: the groups of the range, in the context's order; site_first: the first of every site
+    std::vector<PredictWg> wg;
+    std::vector<int> site_first((size_t)count + 1, 0);
+    size_t gi = 0;
+    if (c->multi) for (int i = 0; i < k0; ++i) gi += (size_t)c->g_cnt[i];
+    for (int j = 0; j < count; ++j) {
+        const int k = k0 + j, ng = c->multi ? c->g_cnt[k] : 1;
+        for (int g = 0; g < ng; ++g) {
+            const int64_t lo = c->multi ? c->g_lim[gi + g] : c->k_lim[k], hi = c->multi ? c->g_lim[gi + g + 1] : c->k_lim[k + 1];
+            wg.push_back(PredictWg{j, g, (int)lo, (int)(hi - lo)});
+        }
+        gi += (size_t)ng;
+        site_first[(size_t)j + 1] = (int)wg.size();
+    }
+    const size_t ng_all = wg.size(), n_draws = ng_all * 3 * (size_t)S, n_grp = ng_all * EPX_PC_COUNT,
+                 n_site = (size_t)count * EPX_PC_COUNT, lds = ppc_lds_bytes(a.p.m.KP, S);
+    a.ngroups = (int)ng_all;
+    HIPCHK(c->ppc_ws.grow(n_draws + n_grp + n_site));
+    HIPCHK(c->pred_iws.grow(4 * ng_all + site_first.size()));
+    a.per_draw = c->ppc_ws; a.out_groups = a.per_draw + n_draws; a.out_sites = a.out_groups + n_grp;
+    int *wg_d = c->pred_iws, *first_d = wg_d + 4 * ng_all;
+    if (set_lds(k_ppc, lds)) return -1;
+    StreamSync sync{c->stream};          // (`wg` and `site_first` are this frame's: the guard is declared behind them)
+    if (upload_draws(c, src, &a.p.draws)) return -1;
+    HIPCHK(hipMemcpyAsync(wg_d, wg.data(), ng_all * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(first_d, site_first.data(), site_first.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    a.p.wg = reinterpret_cast<const PredictWg *>(wg_d); a.site_first = first_d;
+    hipLaunchKernelGGL(k_ppc, dim3(walk_grid(c, ng_all, 4)), dim3(256), lds, c->stream, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_ppc_sites, dim3((unsigned)((count + 15) / 16)), dim3(256), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_groups, a.out_groups, n_grp * 8, hipMemcpyDeviceToHost, c->stream));
+    if (out_sites) HIPCHK(hipMemcpyAsync(out_sites, a.out_sites, n_site * 8, hipMemcpyDeviceToHost, c->stream));
+    if (out_draws) HIPCHK(hipMemcpyAsync(out_draws, a.per_draw, n_draws * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync.finish();
+}
+
 int epx_draw_diagnostics(epx_ctx *c, int k0, int count, const double *theta, int S, int chains, double *out, int *nsamp) {
     CTX(c);
     if (check_range(c, k0, count)) return -1;

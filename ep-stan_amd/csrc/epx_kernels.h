@@ -256,6 +256,32 @@ struct PsisRowsArgs {
 };
 __global__ void k_psis_rows(PsisRowsArgs a);
 
+// Posterior predictive checks of the context's own rows (ppc.inc: k_ppc, k_ppc_sites; include/epx.h: epx_ppc).  A work
+// item of k_ppc is a whole (site, group); it keeps the group's 3 x S per-draw sums in LDS.
+enum { EPX_PC_WAVE_PART = 4 * 3 * 16 };                  // the four waves' partial sums of a slab: [wave][value][column]
+struct PpcArgs {
+    PredictArgs p;                     // model, sizes, draws as k_predict takes them; X: the context's rows; wg: the groups
+                                       // of the call in order (first = row of the context, rows = ALL rows of the group);
+                                       // perm, y, out unused
+    int ngroups;                       // groups of the call (a workgroup takes blockIdx.x, + gridDim.x, ...)
+    int count;                         // sites of the call
+    const int *site_first;             // count + 1: the first group (of the call) of every site
+    const uint8_t *y8;                 // responses of the Bernoulli family ...
+    const double *yd;                  // ... and of the Gaussian one
+    uint64_t seed;
+    long long row0;                    // the stream's row of the context's row i is row0 + i
+    double *per_draw;                  // ngroups x 3 x S: T_rep, D_obs, D_rep of every draw
+    double *out_groups, *out_sites;    // ngroups x EPX_PC_COUNT, count x EPX_PC_COUNT
+};
+// doubles of dynamic LDS in front of the 3 x S per-draw sums: [coefficient slab | log sigma, sigma of the slab | wave
+// partials | wg_reduce scratch | non-finite flag]
+constexpr size_t ppc_fixed_doubles(int KP) { return (size_t)KP * 16 + 32 + EPX_PC_WAVE_PART + 16 + 2; }
+constexpr size_t ppc_lds_bytes(int KP, int S) { return (ppc_fixed_doubles(KP) + (size_t)3 * S) * 8; }
+// most draws per site whose per-draw sums fit the LDS behind the fixed part, 1 KiB left free
+constexpr int ppc_max_draws(int KP) { return (int)((lds_capacity() - 1024 - ppc_fixed_doubles(KP) * 8) / 24); }
+__global__ void k_ppc(PpcArgs a);
+__global__ void k_ppc_sites(PpcArgs a);
+
 // Per-coordinate diagnostics of the draws in device memory (draw_diag.hip; include/epx.h: epx_draw_diagnostics).  A
 // workgroup takes one site and EPX_DG_TILE coordinates; EPX_DG_SLOTS threads per coordinate share its half chains; lags
 // are computed EPX_DG_LAGS at a time.
@@ -316,7 +342,8 @@ __global__ void k_force_pd(ForceArgs a);
 enum { ST_STEPSIZE_MEAN = 0, ST_STEPSIZE_FINAL, ST_NLEAP, ST_NGRAD, ST_NDIV, ST_ACCEPT_MEAN,
        ST_DEPTH_MEAN, ST_FAIL, ST_COUNT };
 enum { K_INIT = 0, K_MOM = 1, K_DIR = 2, K_TOP = 3, K_MERGE = 4, K_SSMOM = 5,
-       K_NEWGROUP = 6 };   // the latents of a new group (newgroup.inc): disjoint from every sampler stream
+       K_NEWGROUP = 6,     // the latents of a new group (newgroup.inc): disjoint from every sampler stream
+       K_PPC = 7 };        // the replicated responses of a posterior predictive check (ppc.inc), likewise
 enum { MAX_DEPTH_CAP = 12 };
 // seconds a workgroup of a pieced launch looks for a site before it reports a lost piece (epx_pieces.h); the environment
 // variable of the same name overrides it at run time (NutsArgs::dyn_wait_s)

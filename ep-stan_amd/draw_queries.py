@@ -5,6 +5,7 @@ the class that runs EP.  Nothing here knows a `Master`:
   QUERIES, HostDraws, Queries   the eight engine methods behind the queries; the host route to each of them, stated once
                                 with `HipEngine`'s argument names and record shapes; and the per-method choice between an
                                 engine's own method and the host route
+  CHECKS                        the engine method behind `Master.ppc`, on both routes and resolved by the same rule
   gather_site_records           the ONLY way per-site records travel between ranks: one flat record per site, padded to the
                                 widest site; gather_named_records packs {name: array} records on top of it
   plan_rows                     predict's rows -> sites arithmetic, pure
@@ -18,11 +19,14 @@ from . import diagnostics as _diagnostics
 from . import loo as _loo
 from . import mix_pred as _mix_pred
 from . import newgroup as _newgroup
+from . import ppc as _ppc
 from . import quantiles as _quantiles
 from . import site_params as _site_params
 
 QUERIES = ('named_moments', 'pooled_count_pass', 'named_order_stats', 'predict', 'predict_new_group', 'loo',
            'draw_diagnostics', 'draw_rank_diagnostics')
+# the engine method behind `Master.ppc`: resolved like QUERIES, kept apart from the eight
+CHECKS = ('replicated_checks',)
 
 
 class HostDraws(object):
@@ -93,6 +97,13 @@ class HostDraws(object):
                                        None if sg else self.j_ind[lo:hi] - 1, self.y[lo:hi])
         return (out, S) if with_n else out
 
+    def replicated_checks(self, seed=0, row0=0, with_n=False, with_draws=False):
+        mid, gauss, sg = self.spec
+        thetas = [self.engine.get_draws(j, all_params=True) for j in range(self.K)]
+        groups, sites, draws = _ppc.ppc_host(mid, self.D, self.site_ng, gauss, thetas, self.X,
+                                             None if sg else self.j_ind - 1, self.y, self.k_lim, seed, row0)
+        return (groups, sites) + ((draws,) if with_draws else ()) + ((thetas[-1].shape[0],) if with_n else ())
+
     def _diagnose(self, record_of, width, with_n):
         """(K, P, width) records of `record_of(theta, chains)`, NaN behind a site's own coordinates, and the used draws."""
         eng, chains = self.engine, self.chains
@@ -120,7 +131,7 @@ class Queries(object):
         self.host = host
 
     def __getattr__(self, name):
-        if name not in QUERIES:
+        if name not in QUERIES and name not in CHECKS:
             raise AttributeError(name)
         engine = self.host.engine
         return getattr(engine if hasattr(engine, name) else self.host, name)
@@ -367,6 +378,27 @@ def sum_loo_rows(comm, loc, lo, hi, N):
     both = comm.allreduce_sum(both)
     rec, code = both[:, :C], both[:, C:]
     return np.where(code == 1.0, np.nan, np.where(code == 2.0, np.inf, np.where(code == 3.0, -np.inf, rec)))
+
+
+# ---- ppc
+
+def gather_checks(comm, site_ng, k_lo, groups, sites, n):
+    """(groups (G, 8), sites (K, 8), ns (K)) of ALL sites from this rank's `replicated_checks` records, those of the
+    sites k_lo, k_lo + 1, ...  A site's flat record is its site record followed by its groups' records: widths differ with
+    `site_ng` (K, all sites), the fill is NaN; the draws per site travel as the head."""
+    C = _ppc.PC_COUNT
+    site_ng = np.asarray(site_ng, dtype=np.int64)
+    K = site_ng.shape[0]
+    if comm.world == 1:
+        return groups, sites, np.full(K, n, dtype=np.int64)
+    flat, at = [], 0
+    for j in range(sites.shape[0]):
+        ng = int(site_ng[k_lo + j])
+        flat.append(np.concatenate((sites[j], groups[at:at + ng].ravel())))
+        at += ng
+    recs, heads = gather_site_records(comm, K, flat, C * (1 + site_ng), np.nan, n)
+    all_groups = np.concatenate([recs[k, C:C * (1 + int(site_ng[k]))].reshape(int(site_ng[k]), C) for k in range(K)])
+    return all_groups, np.ascontiguousarray(recs[:, :C]), np.rint(heads).astype(np.int64)
 
 
 # ---- diagnostics

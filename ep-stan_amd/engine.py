@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 from . import diagnostics as _diagnostics
 from . import loo as _loo
+from . import ppc as _ppc
 from . import site_params as _site_params
 from ._lib import SamplerOpts, check, dptr
 
@@ -596,6 +597,24 @@ class HipEngine(object):
         n = ctypes.c_int()
         check(self.lib.epx_loo(self.ctx, int(k0), int(count), dptr(theta), int(S), dptr(out), ctypes.byref(n)))
         return (out, n.value) if with_n else out
+
+    def replicated_checks(self, seed=0, row0=0, k0=0, count=None, theta=None, with_n=False, with_draws=False):
+        """Posterior predictive check records of the context's own rows of the sites k0..k0+count (epx_ppc,
+        include/epx.h): (groups, sites[, draws][, n]) -- groups (G, 8) one record per (site, group) of the range in the
+        context's order and sites (count, 8), columns ppc.PC_T_OBS .. PC_D_LE; with_draws: also the per-draw T_rep, D_obs,
+        D_rep of every group, (G, 3, S); with_n: also the draws per site.  seed: of the replicates' stream; row0: the
+        stream's row of the context's row 0.  The draws are those of the last sampling call, on the device; `theta`
+        (count, S, P) injects draws instead (test hook)."""
+        count, theta, S = self._draw_range(k0, count, theta)
+        ok = 0 <= k0 and count >= 1 and k0 + count <= self.K        # (a bad range: the library says so)
+        G = (int(self.g_cnt[k0:k0 + count].sum()) if self.g_cnt is not None else count) if ok else 0
+        Sd = (S if theta is not None else self.num_draws()) if with_draws and ok else 0
+        groups, sites = np.zeros((G, _ppc.PC_COUNT)), np.zeros((max(int(count), 0) if ok else 0, _ppc.PC_COUNT))
+        draws = np.zeros((G, 3, Sd)) if with_draws else None
+        n = ctypes.c_int()
+        check(self.lib.epx_ppc(self.ctx, int(k0), int(count), ctypes.c_uint64(int(seed)), int(row0), dptr(theta), int(S),
+                               dptr(groups), dptr(sites), dptr(draws), ctypes.byref(n)))
+        return (groups, sites) + ((draws,) if with_draws else ()) + ((n.value,) if with_n else ())
 
     def psis_rows(self, ll):
         """PSIS of every row of ll (n, S) on this engine's device (epx_psis_rows): (n, 3), columns ELPD, KHAT, WESS."""

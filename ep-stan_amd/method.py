@@ -37,6 +37,7 @@ from . import draw_queries as _dq
 from . import engine as _engine
 from . import loo as _loo
 from . import newgroup as _newgroup
+from . import ppc as _ppc
 from . import quantiles as _quantiles
 from . import reweight as _reweight
 from . import site_params as _site_params
@@ -908,6 +909,50 @@ class Master(object):
         loc, S = self._queries.loo(with_n=True)
         rec = _dq.sum_loo_rows(self.comm, loc, int(self.k_lim[self.k_lo]), int(self.k_lim[self.k_hi]), self.N)
         return _loo.summarise(rec, S, self.k_lim)
+
+    def ppc(self, seed=0, level=0.05, draws=False):
+        """Posterior predictive checks of the fitted site models on the rows they were fitted to, from the tilted draws of
+        the last iteration (include/epx.h, enum epx_ppc, states the definition; the reference has no counterpart): does
+        the model fit the data it was given?  The step between "the chains mixed" (`diagnostics`) and "compare models"
+        (`loo`).  For every draw of a site the responses of its rows are replicated from the model, and per group -- one
+        (site, group within the site); the site itself for an `_sg` model -- two checks are made: T, the sum of the
+        replicated responses against the sum of the observed ones, and D, the realised discrepancy of Gelman, Meng and
+        Stern: the log-likelihood of the replicated responses against that of the observed ones under the same draw.
+
+        What the numbers mean here: the draws of a site come from its TILTED distribution, EP's approximation of the
+        posterior of that site's parameters, so the check is CONDITIONAL on the EP approximation: a small p-value says
+        that the data of the group are unusual under the tilted distribution, whether the model or the approximation is
+        at fault.  Draw s of one site and draw s of another are not a draw of anything: a statistic that pairs them has
+        no meaning, which is why there are records per group and per site and no whole-data total.
+
+        seed: of the replicates' counter-based stream -- a replicate depends on (seed, row, draw) only, so the result
+        does not depend on the number of ranks; level: a group is listed in `extreme` when `p_t` or `p_d` lies outside
+        [level / 2, 1 - level / 2]; draws: also return the per-draw values.
+
+        Returns the dict of `ppc.summarise`.  Per group, G each, in the order of the Master's groups (by site):
+        `group_site`, `t_obs`, `t_rep_mean`, `t_rep_var`, `p_t_ge` = P(T_rep >= T_obs), `p_t` the mid-p
+        (P(T_rep >= T_obs) + P(T_rep > T_obs)) / 2, `d_obs_mean`, `d_rep_mean`, `p_d` = P(D_rep <= D_obs); per site, K
+        each, the same under `site_*` (a site's per-draw values are the sums of its groups'); `n` the draws per site;
+        `level`; `extreme`; with draws=True `draws` (G, 3, n): T_rep, D_obs, D_rep of every (group, draw) -- on one rank
+        only: with several ranks it is refused.  A group with a non-finite linear predictor or log-likelihood has NaN
+        everywhere and is not listed in `extreme`.
+
+        The draws stay in device memory: the kernel k_ppc replicates and adds up a group's rows per draw on chip and
+        reduces them to eight numbers per group.  With several ranks every rank checks its own sites and the records
+        are gathered over the communicator: every rank returns the same dict."""
+        self._need_draws("check replicated data", "nothing can be replicated from them")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+            raise ValueError("`seed`: an integer in [0, 2^64)")
+        if draws and self.comm.world > 1:
+            raise ValueError("`draws=True` returns this rank's per-draw values: with {} ranks it is refused (run on one "
+                             "rank, or use `get_draws`)".format(self.comm.world))
+        if self.N >= 2 ** 32:
+            raise ValueError("{} rows: the replicates' stream counts rows below 2^32".format(self.N))
+        got = self._queries.replicated_checks(seed=int(seed), row0=int(self.k_lim[self.k_lo]), with_n=True,
+                                              with_draws=bool(draws))
+        groups, sites, n = got[0], got[1], got[-1]
+        groups, sites, ns = _dq.gather_checks(self.comm, self._site_ng, self.k_lo, groups, sites, n)
+        return _ppc.summarise(groups, sites, int(ns[0]), self._site_ng, level, got[2] if draws else None)
 
     def diagnostics(self, rank=False):
         """Per-coordinate diagnostics of the tilted draws of the last iteration (include/epx.h, enum epx_diag, states

@@ -439,6 +439,57 @@ int epx_loo(epx_ctx *ctx, int k0, int count, const double *theta, int S, double 
  * leaves the calling thread's current device as it found it. */
 int epx_psis_rows(int device, long long n, int S, const double *ll, double *out /* n x 3 */);
 
+/* Posterior predictive checks of the context's OWN rows from the draws of the sites k0..k0+count (no counterpart in the
+ * reference): the responses are replicated from every draw on the device and a statistic of the replicated data is
+ * compared with the same statistic of the observed data, group by group.  The definition, stated once; the kernels k_ppc /
+ * k_ppc_sites (csrc/ppc.inc) and ppc.ppc_host both follow it.
+ * A GROUP is one (site, group within the site) of the context's rows; for an `_sg` model it is the site.  For group g with
+ * rows i in g and draw s of its site, f_is = alpha_g(s) + x_i . beta_g(s), alpha and beta as EPX_NM_ALPHA / EPX_NM_BETA
+ * form them (EPX_PR_LPD's f).
+ * Replicates.  One per (row, draw), from the samplers' Philox4x32-10 stream at key (seed, chain = 0) and kind 7 = K_PPC --
+ * a kind no sampler uses.  `row` is the context's row index plus row0 (Master passes the index of this rank's first row
+ * among ALL rows: results do not depend on how the sites are sharded); 0 <= row0 and row0 + k_lim[k0 + count] < 2^32.
+ *   Bernoulli-logit family: y_rep_is = 1 if u1 < sigmoid(f_is), else 0, u1 the first uniform of counter (s, K_PPC, row, 0).
+ *   Gaussian family: y_rep_is = f_is + sigma_s z, sigma_s = exp(phi_s[0]), z the standard normal of vector element e = row
+ *   of the samplers' stream: with (u1, u2) the uniforms of counter (s, K_PPC, e >> 1, 0), e the row as a 32-bit signed
+ *   integer, z = sqrt(-2 log u1) cos(2 pi u2) for even e, ... sin ... for odd e.
+ *   A replicate depends on (seed, row, s) only: not on the sites of the call, the number of ranks or the launch grid.
+ * Per (group, draw), with ll the log-likelihood term of EPX_PR_LPD (y f - log(1 + e^f), or the logarithm of the normal
+ * density at mean f and scale sigma_s):
+ *   T_rep_s = sum_i y_rep_is;  D_obs_s = sum_i ll(y_i | s);  D_rep_s = sum_i ll(y_rep_is | s);  per group T_obs = sum_i y_i.
+ *   D is the realised discrepancy of Gelman, Meng & Stern: for the Gaussian family it compares sum ((y - f) / sigma)^2 with
+ *   a chi-square on n_g degrees of freedom, for the Bernoulli family the deviance of the observed responses with that of
+ *   replicated ones.  D_obs_s and D_rep_s are added over the same rows in the same order: where y_rep = y on every row of
+ *   the group they are equal to the bit.
+ * The record of a unit, over the S draws:
+ *   EPX_PC_T_OBS       T_obs;
+ *   EPX_PC_T_MEAN      (sum_s T_rep_s) / S;
+ *   EPX_PC_T_M2        sum_s (T_rep_s - T_MEAN)^2, centred, in a second pass;
+ *   EPX_PC_T_GE, EPX_PC_T_GT   the number of draws with T_rep_s >= T_obs, with T_rep_s > T_obs;
+ *   EPX_PC_D_OBS_MEAN, EPX_PC_D_REP_MEAN   (sum_s D_obs_s) / S, (sum_s D_rep_s) / S;
+ *   EPX_PC_D_LE        the number of draws with D_rep_s <= D_obs_s.
+ *   The three counts are integers held in doubles; the host turns them into p-values (ppc.summarise).
+ * A unit is a group, or a SITE: a site's per-draw values are the sums of its groups' per-draw values, added in group
+ * order, its T_obs likewise; for an `_sg` model the site's record repeats its one group's.  There is no total over sites:
+ * a statistic that pairs draw s of different sites has no meaning.
+ * Results, never faults: a group with a non-finite f, ll(y) or ll(y_rep) in any cell has NaN in all eight columns, and so
+ * has the site that contains it.
+ * out_groups (host, required): groups of the range x EPX_PC_COUNT row-major, in the context's order; out_sites (host, may
+ * be NULL): count x EPX_PC_COUNT; out_draws (host, may be NULL): groups x 3 x S, the per-draw T_rep, D_obs, D_rep of every
+ * group.  The rows, the responses and the group limits are the context's: nothing is uploaded but the work list.
+ * theta == NULL: the draws of the last sampling call (error "no draws yet" before one, and an error when that call did not
+ * cover every site of the range), S is ignored; otherwise TEST HOOK: injected draws (count, S, P) row-major as
+ * epx_named_moments takes them.  nsamp out (may be NULL): draws per site.  At most D = 128 columns and 2^31 - 1 rows.  A
+ * group's 3 x S per-draw sums are kept in LDS: an S beyond (160 KiB - 1 KiB - the fixed part) / 24 bytes (about 6500 at
+ * D = 32) is an error that names S and the limit; there is no fallback.  No floating-point atomics and nothing merged
+ * across workgroups: the same bits on every call, whatever the grid and whichever other sites are in the call.
+ * Stream-ordered, two launches, one synchronisation. */
+enum epx_ppc { EPX_PC_T_OBS = 0, EPX_PC_T_MEAN, EPX_PC_T_M2, EPX_PC_T_GE, EPX_PC_T_GT, EPX_PC_D_OBS_MEAN,
+               EPX_PC_D_REP_MEAN, EPX_PC_D_LE, EPX_PC_COUNT };
+int epx_ppc(epx_ctx *ctx, int k0, int count, uint64_t seed, long long row0, const double *theta, int S,
+            double *out_groups /* groups x EPX_PC_COUNT */, double *out_sites /* count x EPX_PC_COUNT, may be NULL */,
+            double *out_draws /* groups x 3 x S, may be NULL */, int *nsamp);
+
 /* Per-coordinate diagnostics of the draws of the sites k0..k0+count (no counterpart in the reference, which reports the
  * largest split-Rhat of a site and nothing else: EPX_ST_RHAT above stays as it is).  The definition, stated once; the
  * kernel k_draw_diag and diagnostics.diagnostics_host both follow it.  Per site and per sampled coordinate x: every chain
