@@ -117,6 +117,8 @@ SIGNATURES = {
     'epx_psis_rows': (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_int, c_double_p, c_double_p]),
     'epx_ppc': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_longlong, c_double_p,
                                ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
+    'epx_site_evidence': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_longlong,
+                                         c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     'epx_damp_sweep': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, ctypes.c_void_p,
                                       c_double_p, c_double_p, ctypes.c_double, c_double_p, c_double_p, ctypes.c_int,
                                       c_double_p]),

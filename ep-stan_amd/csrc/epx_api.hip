@@ -1629,6 +1629,98 @@ int epx_ppc(epx_ctx *c, int k0, int count, uint64_t seed, long long row0, const 
     return sync.finish();
 }
 
+int epx_site_evidence(epx_ctx *c, int k0, int count, uint64_t seed, long long site0, const double *theta, int S, int chains,
+                      double *out, double *out_terms, double *elapsed_ms) {
+    CTX(c);
+    if (check_range(c, k0, count)) return -1;
+    if (c->D > EPX_PR_DMAX) return fail("epx_site_evidence: D = %d columns, at most %d", c->D, (int)EPX_PR_DMAX);
+    if (!out) return fail("epx_site_evidence: out is required");
+    if (c->N > 0x7fffffff) return fail("epx_site_evidence: %lld rows, at most 2^31 - 1", (long long)c->N);
+    if (site0 < 0 || site0 + (long long)c->K >= (1ll << 31))
+        return fail("epx_site_evidence: site0 = %lld puts the context's %d sites outside [0,2^31)", site0, c->K);
+    EvidenceArgs a;
+    a.m = predict_model(c);
+    const int P = c->P;
+    if (P > evidence_max_coords(a.m.KP))
+        return fail("epx_site_evidence: P = %d sampled coordinates, at most %d at D = %d (the packed factor of the proposal "
+                    "and the slab's workspace are kept in LDS)", P, evidence_max_coords(a.m.KP), c->D);
+    DrawSource src;
+    const int chains_given = chains;
+    if (draw_source(c, "epx_site_evidence", k0, count, theta, S, &chains, &src)) return -1;
+    if (!theta && chains_given != 0 && chains_given != src.chains)       // (the caller sized out_terms by its chains)
+        return fail("epx_site_evidence: chains = %d given, the last sampling call left draws of %d chains", chains_given,
+                    src.chains);
+    S = src.S; chains = src.chains;
+    a.S = S; a.chains = chains; a.n = S / chains; a.nh = a.n / 2;
+    const long long nF = (long long)a.nh * chains;
+    a.N1 = S - (int)nF;
+    if (nF < 2ll * P)
+        return fail("epx_site_evidence: the fit set holds %lld draws (the first %d of each of %d chains), the proposal of "
+                    "P = %d coordinates needs at least %d", nF, a.nh, chains, P, 2 * P);
+    a.M = psis_tail_length(a.N1); a.mfit = psis_fit_points(a.M);
+    const size_t lds_bridge = evidence_bridge_doubles(a.N1, psis_scratch_doubles(a.M)) * 8;
+    if (a.mfit > PSIS_FIT_MAX || lds_bridge > LDS_CAP - 1024)
+        return fail("epx_site_evidence: N1 = %d estimation draws: the terms of the bridge (%zu bytes) do not fit the LDS",
+                    a.N1, lds_bridge);
+    a.k0 = k0; a.pg = c->model == EPX_M1B_SG ? 1 : 1 + c->D;
+    a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    a.X = c->X; a.y8 = c->y; a.yd = c->yd;
+    a.cav_Om = c->cav_Om; a.cav_mu = c->cav_mu;
+    a.seed = seed; a.site0 = site0;
+    // the groups of the range, in the context's order; site_first: the first of every site
+    std::vector<PredictWg> wg;
+    std::vector<int> site_first((size_t)count + 1, 0);
+    size_t gi = 0;
+    if (c->multi) for (int i = 0; i < k0; ++i) gi += (size_t)c->g_cnt[i];
+    for (int j = 0; j < count; ++j) {
+        const int k = k0 + j, ng = c->multi ? c->g_cnt[k] : 1;
+        for (int g = 0; g < ng; ++g) {
+            const int64_t lo = c->multi ? c->g_lim[gi + g] : c->k_lim[k], hi = c->multi ? c->g_lim[gi + g + 1] : c->k_lim[k + 1];
+            wg.push_back(PredictWg{j, g, (int)lo, (int)(hi - lo)});
+        }
+        gi += (size_t)ng;
+        site_first[(size_t)j + 1] = (int)wg.size();
+    }
+    const size_t ng_all = wg.size(), fitw = evidence_fit_doubles(P), n_fit = (size_t)count * fitw,
+                 n_terms = (size_t)count * 2 * a.N1, n_out = (size_t)count * EPX_EV_COUNT,
+                 n_prop = out_terms ? (size_t)count * a.N1 * P : 0;
+    HIPCHK(c->ev_ws.grow(n_fit + n_terms + n_out + n_prop));
+    HIPCHK(c->pred_iws.grow(4 * ng_all + site_first.size()));
+    a.fit = c->ev_ws; a.terms = a.fit + n_fit; a.out = a.terms + n_terms; a.prop = out_terms ? a.out + n_out : nullptr;
+    int *wg_d = c->pred_iws, *first_d = wg_d + 4 * ng_all;
+    const size_t lds_fit = (evidence_packed(P) + 2 * P + 2) * 8, lds_terms = evidence_terms_doubles(P, a.m.KP) * 8;
+    if (set_lds(k_ev_fit, lds_fit) || set_lds(k_ev_terms, lds_terms) || set_lds(k_ev_bridge, lds_bridge)) return -1;
+    StreamSync sync{c->stream};          // (`wg` and `site_first` are this frame's: the guard is declared behind them)
+    if (upload_draws(c, src, &a.draws)) return -1;
+    HIPCHK(hipMemcpyAsync(wg_d, wg.data(), ng_all * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(first_d, site_first.data(), site_first.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    a.wg = reinterpret_cast<const PredictWg *>(wg_d); a.site_first = first_d;
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(k_ev_fit, dim3((unsigned)count), dim3(256), lds_fit, c->stream, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_ev_terms, dim3((unsigned)count), dim3(256), lds_terms, c->stream, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_ev_bridge, dim3((unsigned)count), dim3(256), lds_bridge, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    HIPCHK(hipMemcpyAsync(out, a.out, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    if (out_terms) {
+        // per site [l1, l2 | m, L packed | proposal draws]: three strided copies
+        const size_t w_t = (size_t)2 * a.N1, w_f = fitw - 2, w_p = (size_t)a.N1 * P, width = (w_t + w_f + w_p) * 8;
+        HIPCHK(hipMemcpy2DAsync(out_terms, width, a.terms, w_t * 8, w_t * 8, (size_t)count, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpy2DAsync(out_terms + w_t, width, a.fit, fitw * 8, w_f * 8, (size_t)count, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpy2DAsync(out_terms + w_t + w_f, width, a.prop, w_p * 8, w_p * 8, (size_t)count, hipMemcpyDeviceToHost,
+                                c->stream));
+    }
+    if (sync.finish()) return -1;
+    if (elapsed_ms) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *elapsed_ms = ms;
+    }
+    return 0;
+}
+
 int epx_draw_diagnostics(epx_ctx *c, int k0, int count, const double *theta, int S, int chains, double *out, int *nsamp) {
     CTX(c);
     if (check_range(c, k0, count)) return -1;

@@ -128,6 +128,7 @@ struct epx_ctx {
     DevBuf<int> pred_iws;           // ... [workgroup records (4 ints each) | sorted position -> row (n)]
     DevBuf<double> loo_ws;          // epx_loo: [results (rows x EPX_LO_COUNT) | log-likelihood slabs, one per workgroup, when LDS is too small]
     DevBuf<double> ppc_ws;          // epx_ppc: [per-draw sums (groups x 3 x S) | group records | site records (x EPX_PC_COUNT)]
+    DevBuf<double> ev_ws;           // epx_site_evidence: [proposal fits | terms l1, l2 | records (x EPX_EV_COUNT) | proposal draws, when asked for]
     DevBuf<double> diag_out;        // epx_draw_diagnostics: the call's records (count x P x EPX_DG_COUNT)
     DevBuf<double> rank_out;        // epx_draw_rank_diagnostics: the call's records (count x P x EPX_RD_COUNT)
     DevBuf<double> order_out;       // epx_named_order_stats: the call's order statistics (count x L x n_ranks)

@@ -1,7 +1,7 @@
 // Private to libepx.so (host only): what every entry point that post-processes draws has in front of its kernel --
 // epx_named_moments, epx_named_order_stats, epx_pooled_count_pass, epx_predict, epx_predict_new_group, epx_loo, epx_ppc,
-// epx_draw_diagnostics, epx_draw_rank_diagnostics and epx_pooled_moments.  The draws are those the last sampling call
-// left in c->draws, or `theta` (count, S, P) of the caller, copied to c->inj.  Behind them: what the predictive entries
+// epx_site_evidence, epx_draw_diagnostics, epx_draw_rank_diagnostics and epx_pooled_moments.  The draws are those the last
+// sampling call left in c->draws, or `theta` (count, S, P) of the caller, copied to c->inj.  Behind them: what the predictive entries
 // (epx_predict, epx_predict_new_group, epx_loo, epx_ppc) share in front of the row-tile walk of predict_tile.h.
 // Order of refusals in an entry: its own arguments; for the named entries the name list, then every name in turn; the
 // draw source (draw_source: S, chains, "no draws yet", the sites drawn); whatever the entry derives from S; and only
@@ -23,7 +23,7 @@ struct DrawSource {
 };
 
 // Pure (no HIP call): refuses, or says how many draws per site the call has and where they are.  chains: NULL, or the
-// chains of injected draws (epx_draw_diagnostics); draws of the sampler come in c->s_chains chains.
+// chains of injected draws (epx_draw_diagnostics, epx_site_evidence); draws of the sampler come in c->s_chains chains.
 inline int draw_source(const epx_ctx *c, const char *who, int k0, int count, const double *theta, int S, const int *chains,
                        DrawSource *src) {
     src->theta = theta;

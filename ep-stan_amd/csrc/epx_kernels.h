@@ -282,6 +282,50 @@ constexpr int ppc_max_draws(int KP) { return (int)((lds_capacity() - 1024 - ppc_
 __global__ void k_ppc(PpcArgs a);
 __global__ void k_ppc_sites(PpcArgs a);
 
+// The site normaliser by bridge sampling (evidence.hip: k_ev_fit, k_ev_bridge; evidence_terms.inc: k_ev_terms; include/epx.h:
+// epx_site_evidence).  One workgroup per site in all three kernels.
+struct EvidenceArgs {
+    PredictModel m;
+    int S, chains, n, nh;              // draws per site; n = S / chains per chain, the first nh = n / 2 of a chain are F
+    int N1;                            // |E| = chains x (n - nh) = N2
+    int k0;                            // first site (absolute: indexes site_g0, the cavities)
+    int pg;                            // coordinates per group: 1 (m1) or 1 + D
+    const int *site_g0;                // prefix sums of the groups per site, or NULL: one group everywhere
+    const double *draws;               // site b of the call at draws + b * S * P: (S, P) row-major, chain-major
+    const PredictWg *wg;               // the groups of the call in order (first = row of the context, rows = ALL rows)
+    const int *site_first;             // count + 1: the first group (of the call) of every site
+    const double *X;                   // the context's rows
+    const uint8_t *y8;                 // responses of the Bernoulli family ...
+    const double *yd;                  // ... and of the Gaussian one
+    const double *cav_Om, *cav_mu;     // K x d x d (column-major), K x d: the context's cavities
+    uint64_t seed;
+    long long site0;                   // the stream's chain of site k of the context is site0 + k
+    double *fit;                       // count x evidence_fit_doubles(P): [m (P) | L packed by rows | sum log L_ii, ok]
+    double *terms;                     // count x 2 N1: l1, l2
+    double *prop;                      // NULL, or count x N1 x P: the proposal draws
+    double *out;                       // count x EPX_EV_COUNT
+    int M, mfit;                       // psis_tail_length(N1), psis_fit_points(M)
+};
+constexpr size_t evidence_packed(int P) { return (size_t)P * (P + 1) / 2; }
+constexpr size_t evidence_fit_doubles(int P) { return (size_t)P + evidence_packed(P) + 2; }
+constexpr int evidence_stride(int P) { return P | 1; }   // doubles per column of a slab's records in LDS (odd: banks)
+// doubles of dynamic LDS of k_ev_terms: [L packed | m (P) | mu (P) | theta of the slab's 16 columns | their z or L^-1 (theta
+// - m) | coefficient slab | log sigma, sigma | wave partials (4 x 16) | sums, base (16 each)]; k_ev_fit needs less
+constexpr size_t evidence_terms_doubles(int P, int KP) {
+    return evidence_packed(P) + (size_t)2 * P + (size_t)32 * evidence_stride(P) + (size_t)KP * 16 + 32 + 64 + 32;
+}
+// most sampled coordinates whose packed factor and workspace fit the LDS, 1 KiB left free
+constexpr int evidence_max_coords(int KP) {
+    int P = 1;
+    while (evidence_terms_doubles(P + 1, KP) * 8 <= lds_capacity() - 1024) ++P;
+    return P;
+}
+// doubles of dynamic LDS of k_ev_bridge: [l1 | l2 | -l2 | the iteration's terms (2 N1) | PSIS scratch | reduction scratch]
+constexpr size_t evidence_bridge_doubles(int N1, int psis_scratch) { return (size_t)5 * N1 + psis_scratch + 16; }
+__global__ void k_ev_fit(EvidenceArgs a);
+__global__ void k_ev_terms(EvidenceArgs a);
+__global__ void k_ev_bridge(EvidenceArgs a);
+
 // Per-coordinate diagnostics of the draws in device memory (draw_diag.hip; include/epx.h: epx_draw_diagnostics).  A
 // workgroup takes one site and EPX_DG_TILE coordinates; EPX_DG_SLOTS threads per coordinate share its half chains; lags
 // are computed EPX_DG_LAGS at a time.
@@ -343,7 +387,8 @@ enum { ST_STEPSIZE_MEAN = 0, ST_STEPSIZE_FINAL, ST_NLEAP, ST_NGRAD, ST_NDIV, ST_
        ST_DEPTH_MEAN, ST_FAIL, ST_COUNT };
 enum { K_INIT = 0, K_MOM = 1, K_DIR = 2, K_TOP = 3, K_MERGE = 4, K_SSMOM = 5,
        K_NEWGROUP = 6,     // the latents of a new group (newgroup.inc): disjoint from every sampler stream
-       K_PPC = 7 };        // the replicated responses of a posterior predictive check (ppc.inc), likewise
+       K_PPC = 7,          // the replicated responses of a posterior predictive check (ppc.inc), likewise
+       K_BRIDGE = 8 };     // the proposal draws of the bridge-sampling evidence estimate (evidence.hip), likewise
 enum { MAX_DEPTH_CAP = 12 };
 // seconds a workgroup of a pieced launch looks for a site before it reports a lost piece (epx_pieces.h); the environment
 // variable of the same name overrides it at run time (NutsArgs::dyn_wait_s)

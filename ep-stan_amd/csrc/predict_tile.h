@@ -1,6 +1,6 @@
-// The row-tile walk of the predictive kernels, defined ONCE: k_predict, k_loo (predict.hip), k_newgroup (newgroup.inc) and
-// k_ppc (ppc.inc) differ in where a slab's coefficient columns come from and in what they do with a log-likelihood, not
-// in the walk.
+// The row-tile walk of the predictive kernels, defined ONCE: k_predict, k_loo (predict.hip), k_newgroup (newgroup.inc),
+// k_ppc (ppc.inc) and k_ev_terms (evidence_terms.inc) differ in where a slab's coefficient columns come from and in what
+// they do with a log-likelihood, not in the walk.
 //
 // A wave holds a tile of 16 rows in registers as the A operand of v_mfma_f64_16x16x4_f64 (operand layout: k_moments,
 // dense.hip): lane = (row lane & 15, k lane >> 4) of every step, a leading 1 that takes alpha, zeros behind 1 + D.  The

@@ -16,6 +16,7 @@ the class that runs EP.  Nothing here knows a `Master`:
 import numpy as np
 
 from . import diagnostics as _diagnostics
+from . import evidence as _evidence
 from . import loo as _loo
 from . import mix_pred as _mix_pred
 from . import newgroup as _newgroup
@@ -399,6 +400,36 @@ def gather_checks(comm, site_ng, k_lo, groups, sites, n):
     recs, heads = gather_site_records(comm, K, flat, C * (1 + site_ng), np.nan, n)
     all_groups = np.concatenate([recs[k, C:C * (1 + int(site_ng[k]))].reshape(int(site_ng[k]), C) for k in range(K)])
     return all_groups, np.ascontiguousarray(recs[:, :C]), np.rint(heads).astype(np.int64)
+
+
+# ---- log_evidence
+
+def site_evidence_records(host, seed, site0):
+    """(records (K_local, EV_COUNT), ms) of this rank's sites from the draws of the last sampling call: the engine's
+    `site_evidence` where it has one, else `evidence.site_evidence_host` over its `get_draws` and `get_cavity` (host: the
+    HostDraws of the Master)."""
+    engine = host.engine
+    if hasattr(engine, 'site_evidence'):
+        out, _, ms = engine.site_evidence(seed=seed, site0=site0)
+        return out, ms
+    mid, gauss, sg = host.spec
+    out = np.empty((host.K, _evidence.EV_COUNT))
+    for j in range(host.K):
+        lo, hi = int(host.k_lim[j]), int(host.k_lim[j + 1])
+        P = _evidence.site_dims(mid, host.D, gauss, int(host.site_ng[j]))[1]
+        theta = np.ascontiguousarray(engine.get_draws(j, all_params=True))[:, :P]
+        Om, mu = engine.get_cavity(j)
+        out[j] = _evidence.site_evidence_host(mid, host.D, gauss, host.X[lo:hi], host.y[lo:hi],
+                                              None if sg else host.j_ind[lo:hi] - 1, mu, Om, theta, host.chains, seed,
+                                              site0 + j)[0]
+    return out, 0.0
+
+
+def gather_evidence(comm, K, local):
+    """(K, width) records of ALL sites from this rank's `local` (K_local, width)."""
+    if comm.world == 1:
+        return local
+    return gather_site_records(comm, K, list(local), np.full(K, local.shape[1], dtype=np.int64), np.nan)[0]
 
 
 # ---- diagnostics

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib
 from . import diagnostics as _diagnostics
+from . import evidence as _evidence
 from . import loo as _loo
 from . import ppc as _ppc
 from . import site_params as _site_params
@@ -615,6 +616,32 @@ class HipEngine(object):
         check(self.lib.epx_ppc(self.ctx, int(k0), int(count), ctypes.c_uint64(int(seed)), int(row0), dptr(theta), int(S),
                                dptr(groups), dptr(sites), dptr(draws), ctypes.byref(n)))
         return (groups, sites) + ((draws,) if with_draws else ()) + ((n.value,) if with_n else ())
+
+    def site_evidence(self, seed=0, site0=0, k0=0, count=None, theta=None, chains=None, with_terms=False):
+        """Bridge-sampling records of the sites k0..k0+count (epx_site_evidence, include/epx.h): (out, terms, ms) -- out
+        (count, 6), columns evidence.EV_LOGZ, EV_LOGZ_IS, EV_ITERS, EV_RE2, EV_KHAT, EV_N1; terms: None, or with_terms the
+        list of every site's dict of `evidence.cut_terms` (l1, l2, m, L, proposal draws; it needs `chains`); ms: the device
+        time of the three kernels.  seed: of the proposal draws' stream; site0: the index of the context's first site among all sites.
+        The draws are those of the last sampling call, on the device (`chains`, where given, has to be that call's: the
+        buffer of the terms is sized by it and the library refuses another value); `theta` (count, S, P), chain-major, with
+        `chains` injects draws instead (test hook)."""
+        if (theta is not None or with_terms) and chains is None:
+            raise ValueError('injected draws, and `with_terms`, need `chains`')
+        count, theta, S = self._draw_range(k0, count, theta)
+        ok = 0 <= k0 and count >= 1 and k0 + count <= self.K        # (a bad range: the library says so)
+        out = np.zeros((max(int(count), 0) if ok else 0, _evidence.EV_COUNT))
+        terms = None
+        if with_terms and ok:
+            Sd, ch = S if theta is not None else self.num_draws(), int(chains)
+            N1 = _evidence.split_sizes(Sd, ch)[1] if Sd > 0 and ch > 0 and Sd % ch == 0 else 0
+            terms = np.zeros((int(count), _evidence.terms_width(N1, self.P)))
+        ms = ctypes.c_double()
+        check(self.lib.epx_site_evidence(self.ctx, int(k0), int(count), ctypes.c_uint64(int(seed)), int(site0), dptr(theta),
+                                         int(S), 0 if chains is None else int(chains), dptr(out), dptr(terms),
+                                         ctypes.byref(ms)))
+        if terms is not None:
+            terms = [_evidence.cut_terms(row, N1, self.P) for row in terms]
+        return out, terms, ms.value
 
     def psis_rows(self, ll):
         """PSIS of every row of ll (n, S) on this engine's device (epx_psis_rows): (n, 3), columns ELPD, KHAT, WESS."""

@@ -35,6 +35,7 @@ from . import dispatch as _dispatch
 from . import dist as _dist
 from . import draw_queries as _dq
 from . import engine as _engine
+from . import evidence as _evidence
 from . import loo as _loo
 from . import newgroup as _newgroup
 from . import ppc as _ppc
@@ -953,6 +954,88 @@ class Master(object):
         groups, sites, n = got[0], got[1], got[-1]
         groups, sites, ns = _dq.gather_checks(self.comm, self._site_ng, self.k_lo, groups, sites, n)
         return _ppc.summarise(groups, sites, int(ns[0]), self._site_ng, level, got[2] if draws else None)
+
+    def log_evidence(self, seed=0):
+        """The EP approximation of the log marginal likelihood log p(y) of the whole model at the CURRENT approximation
+        (include/epx.h, epx_site_evidence, states the per-site definition; the reference has no counterpart): what ranks
+        the five nested models as whole models, where `loo` scores rows.  EP's evidence is log Z_EP = Phi(Q, r) -
+        Phi(Q0, r0) + sum_k [log Z_k + Phi(Q - Qi_k, r - ri_k) - Phi(Q, r)], Phi the log normaliser of a Gaussian in
+        natural parameters (`evidence.log_partition`) and Z_k the integral of site k's likelihood and latent prior against
+        its normalised cavity.  Z_k has no closed form: it is estimated per site on the device by bridge sampling between
+        the site's tilted draws and a Gaussian proposal fitted to them (`evidence.site_evidence_host` states it in NumPy).
+
+        The value belongs to the approximation the Master holds now.  It is the fixed-point value of EP's evidence only
+        once EP has converged: at an earlier iteration the sites and the cavities do not yet agree, and the number moves
+        with further iterations.
+
+        seed: of the sampling launch's per-site seeds and of the proposal draws' counter-based stream; a proposal draw
+        depends on (seed, site, draw, coordinate) only, so the per-site estimates do not depend on the number of ranks
+        given the draws.  The seed does NOT make the call reproducible: with the default `init_prev` the launch starts
+        every chain from the last positions of the sampling call before it, so two calls in a row with the same seed
+        sample different draws and return values that differ by the estimate's Monte-Carlo error (with the oracle engine
+        on two small sites: -16.9136, then -16.9058).
+
+        This launches one sampling call of this rank's sites with the workers' own sampler options against the current
+        cavities -- no moment stage: `dQi`, `dri`, the tilted moments and `iter` are untouched.  AFTERWARDS THE DRAWS OF
+        THE LAST SAMPLING CALL ARE THIS LAUNCH'S, with the same number of draws per site: `mix_pred`, `loo`, `ppc` and the
+        other draw queries then read draws against the current cavities, not those of the last iteration.  It also
+        changes where the next `run` iteration starts: with `init_prev` its chains start from this launch's last
+        positions instead of the last iteration's, so a `run` behind a `log_evidence` does not sample the draws it would
+        have sampled without it (under `adapt='carry'` the carried step sizes and metrics are this launch's too).
+
+        Refused at iteration 0, with a sample injector set, when a local worker is not in phase 1 (its cavity is not
+        the current one), and -- a ValueError that names the iterations the sampler needs -- when the first half of the
+        chains holds fewer than 2 P draws for the proposal's covariance.
+
+        Returns a dict, the same on every rank: `log_evidence`; per site, K each: `site_log_z` (log Z_k against the
+        normalised cavity and the normalised latent prior), `re2` (the relative mean-square error of Z_k that treats the
+        draws as independent: the chains' autocorrelation is not in it), `khat` (PSIS k-hat of the proposal's importance
+        ratios; above 0.7 the proposal's tails are too light for the site), `iters` (bridge iterations, 1001: not
+        converged); `n_bad` the sites with a NaN record or 1001 iterations (`log_evidence` is NaN then); `ms` the device
+        time of this rank's evidence kernels (the sampling launch in front of them is not in it)."""
+        if self.iter == 0:
+            raise RuntimeError("Can not estimate the evidence before at least one iteration has been done.")
+        if self._sample_injector is not None:
+            raise RuntimeError("A sample injector is set (`_sample_injector`): its draws hold phi only, the evidence "
+                               "needs draws of every sampled coordinate.")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < MAX_UINT:
+            raise ValueError("`seed`: an integer in [0, {})".format(MAX_UINT))
+        local_workers = self.workers[self.k_lo:self.k_hi]
+        for w in local_workers:
+            if w.phase != 1:
+                raise RuntimeError("Worker {} is in phase {}: the evidence needs the current cavity of every site "
+                                   "(phase 1).".format(w.index, w.phase))
+        eng, w0 = self.engine, local_workers[0]
+        sp = w0.stan_params
+        opts = w0._sampler_opts()
+        warmup = sp['iter'] // 2 if sp['warmup'] is None else sp['warmup']
+        nkeep = (sp['iter'] - warmup + sp['thin'] - 1) // sp['thin']
+        P = int(eng.P)
+        if (nkeep // 2) * sp['chains'] < 2 * P:
+            need = 2 * -(-2 * P // sp['chains'])
+            raise ValueError("the first half of {} chains of {} kept draws holds {} draws, the proposal of P = {} sampled "
+                             "coordinates needs {}: sample at least {} kept iterations per chain (iter - warmup >= {} "
+                             "at thin = {})".format(sp['chains'], nkeep, (nkeep // 2) * sp['chains'], P, 2 * P, need,
+                                                    need * sp['thin'], sp['thin']))
+        sseeds = stan_seeds(run_seeds(int(seed), 1, self.K)[0, self.k_lo:self.k_hi])
+        eng.sample_batch(sseeds, opts)
+        self._draws_injected = False
+        rec, ms = _dq.site_evidence_records(self._queries.host, int(seed), int(self.k_lo))
+        mid, gauss, _ = self._site_spec()
+        local = np.empty((self.K_local, 5))
+        for j in range(self.K_local):
+            k = self.k_lo + j
+            Om = eng.get_cavity(j)[0]
+            local[j, 0] = _evidence.site_log_z(rec[j, _evidence.EV_LOGZ], Om,
+                                               _evidence.n_latents(mid, self.D, int(self._site_ng[k])), mid)
+            local[j, 1:4] = rec[j, [_evidence.EV_RE2, _evidence.EV_KHAT, _evidence.EV_ITERS]]
+            local[j, 4] = _evidence.log_partition(self.Q - self.Qi[:, :, k], self.r - self.ri[:, k])
+        full = _dq.gather_evidence(self.comm, self.K, local)
+        iters = full[:, 3]
+        n_bad = int(np.sum(~np.isfinite(full[:, 0]) | (iters > _evidence.MAX_ITERS)))
+        return dict(log_evidence=_evidence.combine_parts(self.Q, self.r, self.Q0, self.r0, full[:, 0], full[:, 4]),
+                    site_log_z=full[:, 0].copy(), re2=full[:, 1].copy(), khat=full[:, 2].copy(), iters=iters.copy(),
+                    n_bad=n_bad, ms=ms)
 
     def diagnostics(self, rank=False):
         """Per-coordinate diagnostics of the tilted draws of the last iteration (include/epx.h, enum epx_diag, states

@@ -490,6 +490,69 @@ int epx_ppc(epx_ctx *ctx, int k0, int count, uint64_t seed, long long row0, cons
             double *out_groups /* groups x EPX_PC_COUNT */, double *out_sites /* count x EPX_PC_COUNT, may be NULL */,
             double *out_draws /* groups x 3 x S, may be NULL */, int *nsamp);
 
+/* The site normaliser of EP, log Z_k, by bridge sampling on the device (no counterpart in the reference, which has no
+ * evidence estimate).  The definition, stated once; the kernels k_ev_fit / k_ev_bridge (csrc/evidence.hip), k_ev_terms
+ * (csrc/evidence_terms.inc) and evidence.site_evidence_host all follow it.  What is estimated per site is log int exp(lq), lq the UNNORMALISED log
+ * density the site's sampler draws from; evidence.site_log_z and evidence.combine turn the sites' values into log Z_EP.
+ * Draws and cavity.  Site k has P_k sampled coordinates theta = [phi (d) | lambda], lambda = eta per group, then etb per
+ *   group x D, as epx_named_moments lays them out (P_k = P for a single-group context; a multi-group site uses its own
+ *   d + groups x (1 or 1 + D) coordinates).  Its S draws come in the device's order, chain-major: `chains` chains of
+ *   n = S / chains draws.  Its cavity (mu, Omega) is the context's current one (epx_get_cavity).
+ * Split.  The fit set F is the first floor(n / 2) draws of every chain, the estimation set E the rest, both in the
+ *   device's order; N1 = |E|, N2 = N1.
+ * Proposal.  m = the mean over F; C = the centred scatter over F / (|F| - 1), from a second pass (never sum theta theta'
+ *   - n m m'); L = the lower Cholesky factor of C.
+ * Proposal draws.  theta~_r = m + L z_r, r < N2, z_{r,e} the standard normal of element e of the samplers' Philox4x32-10
+ *   stream at key (seed, chain = site0 + k), k the site's index in the context, counter (r, kind 8 = K_BRIDGE, e >> 1, 0):
+ *   with (u1, u2) its uniforms, z = sqrt(-2 log u1) cos(2 pi u2) for even e, ... sin ... for odd e (epx_predict_new_group
+ *   states the same pair).  site0 is the index of the context's first site among ALL sites of all ranks, 0 <= site0 and
+ *   site0 + K < 2^31: a site's record does not depend on the sharding.
+ * Target.  lq(theta) = -1/2 (phi - mu)' Omega (phi - mu) + lprior(lambda) + sum_{i in site} ll_i(theta), lprior =
+ *   -1/2 |lambda|^2 (m1..m4) or -|lambda|_1 (m5), ll_i the log-likelihood term of EPX_PR_LPD with f from EPX_NM_ALPHA /
+ *   EPX_NM_BETA of the row's group.  Logistic family: lq is the sampler's lp.  Gaussian family: the sampler's lp minus
+ *   n_k 1/2 log 2 pi (the sampler drops that constant, EPX_PR_LPD keeps it).
+ * Proposal density.  lg(theta) = -1/2 |L^-1 (theta - m)|^2 - sum log L_ii - (P_k / 2) log 2 pi; for a proposal draw the
+ *   quadratic form is |z_r|^2 taken from z itself.
+ * Terms.  l1_s = lq(theta_s) - lg(theta_s), s in E;  l2_r = lq(theta~_r) - lg(theta~_r).
+ * Bridge (Meng & Wong's optimal bridge), in log space: s1 = N1 / (N1 + N2), s2 = N2 / (N1 + N2), LSE2(a, b) = t +
+ *   log(e^(a - t) + e^(b - t)) about t = max(a, b);
+ *     rho_0 = LSE_r(l2_r) - log N2
+ *     rho_{t+1} = [LSE_r(l2_r - LSE2(log s1 + l2_r, log s2 + rho_t)) - log N2]
+ *               - [LSE_s(-LSE2(log s1 + l1_s, log s2 + rho_t)) - log N1]
+ *   every LSE about its largest term, every sum in a fixed order; stop when |rho_{t+1} - rho_t| <= 1e-10 or after 1000
+ *   iterations.
+ * The record of a site:
+ *   EPX_EV_LOGZ      the final rho: log int exp(lq);
+ *   EPX_EV_LOGZ_IS   rho_0, the plain importance-sampling estimate from the proposal draws;
+ *   EPX_EV_ITERS     iterations used; 1001: not converged;
+ *   EPX_EV_RE2       Var(f2) / (N2 mean(f2)^2) + Var(f1) / (N1 mean(f1)^2), f1_s = 1 / (s1 e^(l1_s - rho) + s2), f2_r =
+ *                    e^(l2_r - rho) / (s1 e^(l2_r - rho) + s2), Var with divisor N - 1, centred in a second pass: the relative
+ *                    mean-square error of e^rho that treats the draws of both sets as INDEPENDENT.  The chains'
+ *                    autocorrelation is not in it: with an effective sample size below N1 the true error is larger;
+ *   EPX_EV_KHAT      the PSIS k-hat of the proposal's importance ratios e^(l2): steps 1-5 of enum epx_loo on ll = -l2 (the
+ *                    same code, psis.h); +inf where the tail is not fitted;
+ *   EPX_EV_N1        N1.
+ * Results, never faults: a site with a non-finite l1 or l2, or whose Cholesky factorisation meets a pivot that is not
+ *   finite or numerically <= 0 -- at most P_k 2^-50 C_jj, what rounding alone leaves of an exact zero (a non-finite draw
+ *   in F, a duplicated coordinate) --, has NaN in LOGZ, LOGZ_IS, RE2 and KHAT and 0 in ITERS;
+ *   the other sites of the call are unaffected.
+ * Refusals, known from sizes alone, before any launch, each naming its numbers: D > 128; a P whose packed factor and
+ *   workspace do not fit the LDS (epx_kernels.h: evidence_max_coords, 166 at D = 32, so m4b's P = 99 is admitted; no
+ *   fallback); chains that do not divide S; |F| < 2 P; an N1 whose terms do not fit the LDS of the bridge.
+ * out (host, required): count x EPX_EV_COUNT.  out_terms (host, may be NULL; the tests read it): per site
+ *   [l1 (N1) | l2 (N1) | m (P) | L packed by rows, L_ij at i (i + 1) / 2 + j (P (P + 1) / 2) | theta~ (N2 x P)], zeros
+ *   behind a multi-group site's own P_k; without it the proposal draws never leave the chip.
+ * theta == NULL: the draws of the last sampling call and its chains (error "no draws yet" before one, and an error when
+ *   that call did not cover every site of the range), S is ignored, and chains is 0 or -- from a caller that sized
+ *   out_terms by it -- the chains of that call: any other value is an error; otherwise TEST HOOK: injected draws
+ *   (count, S, P) row-major, chain-major, with their `chains`.  No floating-point atomics, nothing merged across
+ *   workgroups: the same bits on every call, whichever other sites are in the call.  Stream-ordered, three launches, one
+ *   synchronisation; elapsed_ms (may be NULL): the device time of the three. */
+enum epx_evidence { EPX_EV_LOGZ = 0, EPX_EV_LOGZ_IS, EPX_EV_ITERS, EPX_EV_RE2, EPX_EV_KHAT, EPX_EV_N1, EPX_EV_COUNT };
+int epx_site_evidence(epx_ctx *ctx, int k0, int count, uint64_t seed, long long site0, const double *theta, int S,
+                      int chains, double *out /* count x EPX_EV_COUNT */, double *out_terms /* may be NULL */,
+                      double *elapsed_ms);
+
 /* Per-coordinate diagnostics of the draws of the sites k0..k0+count (no counterpart in the reference, which reports the
  * largest split-Rhat of a site and nothing else: EPX_ST_RHAT above stays as it is).  The definition, stated once; the
  * kernel k_draw_diag and diagnostics.diagnostics_host both follow it.  Per site and per sampled coordinate x: every chain
