@@ -101,6 +101,9 @@ SIGNATURES = {
                                           ctypes.c_int, c_double_p, c_double_p, ctypes.POINTER(ctypes.c_longlong)]),
     'epx_predict': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int64_p, c_int32_p, c_double_p, c_double_p,
                                    c_double_p, ctypes.c_int, c_double_p, c_int_p]),
+    'epx_predict_order_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int64_p, c_int32_p, c_double_p,
+                                               c_int64_p, ctypes.c_int, ctypes.c_uint64, c_int64_p, ctypes.c_int, c_double_p,
+                                               ctypes.c_int, c_double_p, c_int_p]),
     'epx_predict_new_group': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_longlong,
                                              ctypes.c_int, ctypes.c_longlong, c_double_p, c_double_p, c_int32_p, ctypes.c_int,
                                              c_int32_p, c_double_p, ctypes.c_int, c_double_p, c_double_p,

@@ -1388,13 +1388,8 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
     if (check_range(c, k0, count)) return -1;
     if (!row_lim) return fail("epx_predict: row_lim is required");
     if (c->D > EPX_PR_DMAX) return fail("epx_predict: D = %d columns, at most %d", c->D, (int)EPX_PR_DMAX);
-    if (row_lim[0] != 0) return fail("epx_predict: row_lim has to start at 0 (it starts at %lld)", (long long)row_lim[0]);
-    for (int j = 0; j < count; ++j)
-        if (row_lim[j + 1] < row_lim[j])
-            return fail("epx_predict: row_lim has to be non-decreasing (site %d: [%lld,%lld))", k0 + j,
-                        (long long)row_lim[j], (long long)row_lim[j + 1]);
-    const int64_t n = row_lim[count];
-    if (n > 0x7fffffff) return fail("epx_predict: %lld rows in one call, at most 2^31 - 1", (long long)n);
+    int64_t n;
+    if (new_row_count("epx_predict", k0, count, row_lim, &n)) return -1;
     const size_t D = c->D;
     PredictArgs a;
     DrawSource src;
@@ -1406,17 +1401,9 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
         if (const int64_t i = bad_response(c, yn, n, false); i >= 0)
             return fail("epx_predict: row %lld: y = %g, the Bernoulli models take 0 or 1", (long long)i, yn[i]);
     // rows sorted by (site, group), stable: perm[sorted position] = row; then workgroups of <= 64 rows of one (site, group)
-    std::vector<int> perm((size_t)n), first;
+    std::vector<int> perm((size_t)n);
     std::vector<PredictWg> wg;
-    for (int j = 0; j < count; ++j) {
-        const int ng = c->multi ? c->g_cnt[k0 + j] : 1;
-        if (const int64_t i = sort_rows_by_group(row_lim[j], row_lim[j + 1], row_group, ng, perm.data(), first); i >= 0)
-            return fail("epx_predict: row %lld: group %d outside the %d group(s) of site %d", (long long)i,
-                        row_group ? (int)row_group[i] : 0, ng, k0 + j);
-        for (int g = 0; g < ng; ++g)
-            for (int r = first[g]; r < first[g + 1]; r += EPX_PR_WG_ROWS)
-                wg.push_back(PredictWg{j, g, r, first[g + 1] - r < EPX_PR_WG_ROWS ? first[g + 1] - r : (int)EPX_PR_WG_ROWS});
-    }
+    if (cut_new_rows(c, "epx_predict", k0, count, row_lim, row_group, EPX_PR_WG_ROWS, perm.data(), wg)) return -1;
     a.m = predict_model(c); a.S = src.S;
     a.k0 = k0; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
     const size_t nn = (size_t)n, nwg = wg.size();
@@ -1434,6 +1421,101 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
     hipLaunchKernelGGL(k_predict, dim3((unsigned)nwg), dim3(256), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, out_d, nn * EPX_PR_COUNT * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync.finish();
+}
+
+int epx_predict_order_stats(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int32_t *row_group, const double *Xn,
+                            const int64_t *row_id, int what, uint64_t seed, const int64_t *ranks, int n_ranks,
+                            const double *theta, int S, double *out, int *nsamp) {
+    CTX(c);
+    const char *who = "epx_predict_order_stats";
+    if (check_range(c, k0, count)) return -1;
+    if (c->D > EPX_PR_DMAX) return fail("%s: D = %d columns, at most %d", who, c->D, (int)EPX_PR_DMAX);
+    int64_t n;
+    if (new_row_count(who, k0, count, row_lim, &n)) return -1;
+    if (what != EPX_PO_F && what != EPX_PO_YREP)
+        return fail("%s: what = %d, one of EPX_PO_F = %d, EPX_PO_YREP = %d", who, what, (int)EPX_PO_F, (int)EPX_PO_YREP);
+    if (what == EPX_PO_YREP && !c->gauss)
+        return fail("%s: EPX_PO_YREP is defined for the Gaussian family only: a Bernoulli-logit model's 0/1 replicate has no "
+                    "useful quantile", who);
+    if (!ranks || n_ranks < 1 || n_ranks > EPX_QT_MAX_RANKS)
+        return fail("%s: between 1 and %d ranks (got %d)", who, (int)EPX_QT_MAX_RANKS, n_ranks);
+    if (n > 0 && (!Xn || !out)) return fail("%s: Xn and out are required", who);
+    const size_t nn = (size_t)n, D = c->D;
+    std::vector<uint32_t> ids;
+    if (row_id) {
+        ids.resize(nn);
+        for (size_t i = 0; i < nn; ++i) {
+            if (row_id[i] < 0 || row_id[i] >= (1ll << 32))
+                return fail("%s: row %lld: row_id = %lld outside [0,2^32)", who, (long long)i, (long long)row_id[i]);
+            ids[i] = (uint32_t)row_id[i];
+        }
+    }
+    if (what != EPX_PO_YREP) ids.clear();                 // (checked all the same; only the replicates read them)
+    PredOrderArgs a;
+    DrawSource src;
+    if (draw_source(c, who, k0, count, theta, S, nullptr, &src)) return -1;
+    S = src.S;
+    for (int i = 0; i < n_ranks; ++i) {
+        if (ranks[i] < 0 || ranks[i] >= S)
+            return fail("%s: rank %lld outside [0, %d), the draws per site", who, (long long)ranks[i], S);
+        if (i > 0 && ranks[i] <= ranks[i - 1]) return fail("%s: the ranks have to be ascending and distinct", who);
+    }
+    a.p.m = predict_model(c); a.p.S = S;
+    // the keys' share of the LDS: R rows of N(S) keys behind the walk's fixed part
+    size_t budget = pred_order_budget(a.p.m.KP);
+    std::string lowered;                                  // what a refusal says of the variable, where it lowered the budget
+    if (const char *e = getenv("EPX_PO_LDS_BYTES")) {     // (a value that is no whole non-negative number is ignored)
+        char *end = nullptr;
+        const long long v = strtoll(e, &end, 10);
+        if (end != e && *end == '\0' && v >= 0 && (size_t)v < budget) {
+            budget = (size_t)v;
+            lowered = std::string("; EPX_PO_LDS_BYTES = ") + e + " lowers the keys' budget";
+        }
+    }
+    size_t nmax = 0;                                      // the largest power of two of keys that fits: the largest S
+    for (size_t m = 1; m * 8 <= budget; m *= 2) nmax = m;
+    const auto too_many = [&](size_t most) {
+        return fail("%s: S = %d draws per site, at most %d (a row's keys, padded to a power of two, are sorted in LDS%s)", who, S,
+                    (int)most, lowered.c_str());
+    };
+    if ((size_t)S > nmax) return too_many(nmax);
+    a.npad = 2; a.lg = 1;
+    while (a.npad < S) { a.npad *= 2; ++a.lg; }
+    int R = 16;
+    while (R > 1 && (size_t)R * a.npad * 8 > budget) R /= 2;
+    if ((size_t)R * a.npad * 8 > budget) return too_many(0);      // (S = 1 under a budget below two keys)
+    // rows sorted by (site, group), stable: perm[sorted position] = row; then work items of <= R rows of one (site, group)
+    std::vector<int> perm(nn);
+    std::vector<PredictWg> wg;
+    if (cut_new_rows(c, who, k0, count, row_lim, row_group, R, perm.data(), wg)) return -1;
+    if (wg.size() > 0x7fffffff) return fail("%s: %lld work items in one call, at most 2^31 - 1", who, (long long)wg.size());
+    if (nsamp) *nsamp = S;                                // (behind the last refusal: a refusal writes nothing)
+    if (n == 0) return 0;
+    a.p.k0 = k0; a.p.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    a.what = what; a.seed = seed; a.n_ranks = n_ranks;
+    for (int i = 0; i < EPX_QT_MAX_RANKS; ++i) a.rank[i] = i < n_ranks ? (int)ranks[i] : 0;
+    const size_t nwg = wg.size(), lds = pred_order_fixed_bytes(a.p.m.KP) + (size_t)R * a.npad * 8;
+    a.nwg = (int)nwg;
+    HIPCHK(c->pred_ws.grow(nn * D + nn * n_ranks));
+    HIPCHK(c->pred_iws.grow(4 * nwg + nn + (ids.empty() ? 0 : nn)));
+    double *X_d = c->pred_ws, *out_d = X_d + nn * D;
+    int *wg_d = c->pred_iws, *perm_d = wg_d + 4 * nwg, *id_d = perm_d + nn;
+    static_assert(sizeof(uint32_t) == sizeof(int), "the rows' stream indices lie in the int workspace");
+    if (set_lds(k_predict_order, lds)) return -1;
+    StreamSync sync{c->stream};          // (`ids`, `perm` and `wg` are this frame's: the guard is declared behind them)
+    if (upload_draws(c, src, &a.p.draws)) return -1;
+    if (queue_new_rows(c, nn, Xn, nullptr, perm.data(), X_d, nullptr, perm_d)) return -1;
+    HIPCHK(hipMemcpyAsync(wg_d, wg.data(), nwg * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream));
+    if (!ids.empty()) HIPCHK(hipMemcpyAsync(id_d, ids.data(), nn * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    a.p.wg = reinterpret_cast<const PredictWg *>(wg_d); a.p.perm = perm_d;
+    a.p.X = X_d; a.p.y = nullptr; a.p.out = nullptr;
+    a.row_id = ids.empty() ? nullptr : reinterpret_cast<const uint32_t *>(id_d);
+    a.out = out_d;
+    // (the kernel's registers leave room for two workgroups per compute unit, the LDS for one where the keys fill it)
+    hipLaunchKernelGGL(k_predict_order, dim3(walk_grid(c, nwg, 2 * lds <= LDS_CAP ? 2 : 1)), dim3(256), lds, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, out_d, nn * n_ranks * 8, hipMemcpyDeviceToHost, c->stream));
     return sync.finish();
 }
 

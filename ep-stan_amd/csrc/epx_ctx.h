@@ -126,6 +126,8 @@ struct epx_ctx {
     DevBuf<double> pooled_ws;       // epx_pooled_moments: [partial tiles | partial sums | scatter | sum | centre]
     DevBuf<double> pred_ws;         // epx_predict: [new rows (n x D) | responses (n) | results (n x EPX_PR_COUNT)]
     DevBuf<int> pred_iws;           // ... [workgroup records (4 ints each) | sorted position -> row (n)]
+                                    // (epx_predict_order_stats: [new rows | order statistics (n x n_ranks)] and [work items |
+                                    // sorted position -> row | the rows' stream indices (n)] in the same two)
     DevBuf<double> loo_ws;          // epx_loo: [results (rows x EPX_LO_COUNT) | log-likelihood slabs, one per workgroup, when LDS is too small]
     DevBuf<double> ppc_ws;          // epx_ppc: [per-draw sums (groups x 3 x S) | group records | site records (x EPX_PC_COUNT)]
     DevBuf<double> ev_ws;           // epx_site_evidence: [proposal fits | terms l1, l2 | records (x EPX_EV_COUNT) | proposal draws, when asked for]

@@ -1,8 +1,9 @@
 // Private to libepx.so (host only): what every entry point that post-processes draws has in front of its kernel --
-// epx_named_moments, epx_named_order_stats, epx_pooled_count_pass, epx_predict, epx_predict_new_group, epx_loo, epx_ppc,
+// epx_named_moments, epx_named_order_stats, epx_pooled_count_pass, epx_predict, epx_predict_order_stats,
+// epx_predict_new_group, epx_loo, epx_ppc,
 // epx_site_evidence, epx_draw_diagnostics, epx_draw_rank_diagnostics and epx_pooled_moments.  The draws are those the last
 // sampling call left in c->draws, or `theta` (count, S, P) of the caller, copied to c->inj.  Behind them: what the predictive entries
-// (epx_predict, epx_predict_new_group, epx_loo, epx_ppc) share in front of the row-tile walk of predict_tile.h.
+// (epx_predict, epx_predict_order_stats, epx_predict_new_group, epx_loo, epx_ppc) share in front of the row-tile walk of predict_tile.h.
 // Order of refusals in an entry: its own arguments; for the named entries the name list, then every name in turn; the
 // draw source (draw_source: S, chains, "no draws yet", the sites drawn); whatever the entry derives from S; and only
 // then the first copy (upload_draws), behind a StreamSync (epx_ctx.h) -- from there on every exit has synchronised c->stream,
@@ -113,6 +114,37 @@ inline int64_t sort_rows_by_group(int64_t lo, int64_t hi, const int32_t *row_gro
     std::vector<int> at(first.begin(), first.end() - 1);
     for (int64_t i = lo; i < hi; ++i) perm[at[row_group ? row_group[i] : 0]++] = (int)i;
     return -1;
+}
+
+// The limits of the new rows of the sites of a call (epx_predict, epx_predict_order_stats): refuses, or says how many
+// rows there are
+inline int new_row_count(const char *who, int k0, int count, const int64_t *row_lim, int64_t *n) {
+    if (!row_lim) return fail("%s: row_lim is required", who);
+    if (row_lim[0] != 0) return fail("%s: row_lim has to start at 0 (it starts at %lld)", who, (long long)row_lim[0]);
+    for (int j = 0; j < count; ++j)
+        if (row_lim[j + 1] < row_lim[j])
+            return fail("%s: row_lim has to be non-decreasing (site %d: [%lld,%lld))", who, k0 + j,
+                        (long long)row_lim[j], (long long)row_lim[j + 1]);
+    *n = row_lim[count];
+    if (*n > 0x7fffffff) return fail("%s: %lld rows in one call, at most 2^31 - 1", who, (long long)*n);
+    return 0;
+}
+
+// How new rows are cut into work items, stated once: the rows sorted by (site, group), stable -- perm[sorted position] =
+// row (perm: n ints) -- then items of at most `item` rows of ONE (site, group), in that order
+inline int cut_new_rows(const epx_ctx *c, const char *who, int k0, int count, const int64_t *row_lim, const int32_t *row_group,
+                        int item, int *perm, std::vector<PredictWg> &wg) {
+    std::vector<int> first;
+    for (int j = 0; j < count; ++j) {
+        const int ng = c->multi ? c->g_cnt[k0 + j] : 1;
+        if (const int64_t i = sort_rows_by_group(row_lim[j], row_lim[j + 1], row_group, ng, perm, first); i >= 0)
+            return fail("%s: row %lld: group %d outside the %d group(s) of site %d", who, (long long)i,
+                        row_group ? (int)row_group[i] : 0, ng, k0 + j);
+        for (int g = 0; g < ng; ++g)
+            for (int r = first[g]; r < first[g + 1]; r += item)
+                wg.push_back(PredictWg{j, g, r, first[g + 1] - r < item ? first[g + 1] - r : item});
+    }
+    return 0;
 }
 
 // Queues the copies of the n new rows, their responses (if any) and the sort's perm; behind a StreamSync

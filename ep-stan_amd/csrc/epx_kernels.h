@@ -282,6 +282,28 @@ constexpr int ppc_max_draws(int KP) { return (int)((lds_capacity() - 1024 - ppc_
 __global__ void k_ppc(PpcArgs a);
 __global__ void k_ppc_sites(PpcArgs a);
 
+// Order statistics across the draws of every NEW row's linear predictor or replicated response (predict_order.inc: k_predict_order;
+// include/epx.h: epx_predict_order_stats).  A work item is up to `R` rows of one (site, group): their S x R values become
+// keys (order_key.h) in LDS, row rr at rr x npad, and every row is sorted there.
+struct PredOrderArgs {
+    PredictArgs p;                     // model, sizes, draws, new rows, perm and work items as k_predict takes them (first =
+                                       // sorted position, rows <= R); y, out unused
+    int nwg;                           // work items (a workgroup takes blockIdx.x, + gridDim.x, ...)
+    int what;                          // enum epx_pred_order
+    int npad, lg;                      // S rounded up to a power of two, at least 2, and its logarithm
+    int n_ranks;
+    int rank[EPX_QT_MAX_RANKS];        // ascending, distinct, in [0, S)
+    uint64_t seed;
+    const uint32_t *row_id;            // n, the caller's order: the stream's index of every row; NULL: the row itself
+    double *out;                       // n x n_ranks, the caller's order
+};
+// bytes of dynamic LDS in front of the keys, the walk's fixed part: [four times (coefficient slab | log sigma, sigma of the
+// slab): a step of the walk stages 64 draws, one slab per wave | the item's 16 NaN flags]
+constexpr size_t pred_order_fixed_bytes(int KP) { return (4 * ((size_t)KP * 16 + 32) + 8) * 8; }
+// bytes the keys of a work item may take: what is left of the LDS, 1 KiB kept free
+constexpr size_t pred_order_budget(int KP) { return lds_capacity() - 1024 - pred_order_fixed_bytes(KP); }
+__global__ void k_predict_order(PredOrderArgs a);
+
 // The site normaliser by bridge sampling (evidence.hip: k_ev_fit, k_ev_bridge; evidence_terms.inc: k_ev_terms; include/epx.h:
 // epx_site_evidence).  One workgroup per site in all three kernels.
 struct EvidenceArgs {
@@ -388,7 +410,8 @@ enum { ST_STEPSIZE_MEAN = 0, ST_STEPSIZE_FINAL, ST_NLEAP, ST_NGRAD, ST_NDIV, ST_
 enum { K_INIT = 0, K_MOM = 1, K_DIR = 2, K_TOP = 3, K_MERGE = 4, K_SSMOM = 5,
        K_NEWGROUP = 6,     // the latents of a new group (newgroup.inc): disjoint from every sampler stream
        K_PPC = 7,          // the replicated responses of a posterior predictive check (ppc.inc), likewise
-       K_BRIDGE = 8 };     // the proposal draws of the bridge-sampling evidence estimate (evidence.hip), likewise
+       K_BRIDGE = 8,       // the proposal draws of the bridge-sampling evidence estimate (evidence.hip), likewise
+       K_PRED_REP = 9 };   // the replicated responses of new rows (predict_order.inc), likewise
 enum { MAX_DEPTH_CAP = 12 };
 // seconds a workgroup of a pieced launch looks for a site before it reports a lost piece (epx_pieces.h); the environment
 // variable of the same name overrides it at run time (NutsArgs::dyn_wait_s)

@@ -1,7 +1,8 @@
 // The total order of the draws of one element (include/epx.h: "Posterior quantiles"): a double is ordered by the key
 // k(x) = its IEEE-754 bits as uint64, all bits flipped when the sign bit is set, the sign bit set otherwise, so that
-// -inf < ... < -0.0 < +0.0 < ... < +inf as unsigned integers.  Included by quantiles.inc and by rank_diag.hip, which
-// ranks a coordinate's draws by the same keys; quantiles.py (key_of / value_of) states the same in NumPy.
+// -inf < ... < -0.0 < +0.0 < ... < +inf as unsigned integers.  Included by quantiles.inc, by rank_diag.hip, which
+// ranks a coordinate's draws by the same keys, and by predict.hip for predict_order.inc; quantiles.py (key_of / value_of)
+// states the same in NumPy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

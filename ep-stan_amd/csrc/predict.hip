@@ -8,10 +8,11 @@
 // A workgroup of four waves takes up to 64 rows of ONE (site, group), a tile of 16 rows per wave (the host sorted the
 // rows and cut them: PredictWg), and walks the site's draws in slabs of 16, twice: the row-tile walk of predict_tile.h,
 // which states the tile, the slab step, the two passes' sums and the row record.  This file adds where a slab's columns
-// come from: predict_stage, the site's draws.  k_newgroup (newgroup.inc), k_loo (below), k_ppc (ppc.inc) and k_ev_terms
-// (evidence_terms.inc) walk the same tile.
+// come from: predict_stage, the site's draws.  k_newgroup (newgroup.inc), k_loo (below), k_ppc (ppc.inc), k_predict_order
+// (predict_order.inc) and k_ev_terms (evidence_terms.inc) walk the same tile.
 #include "predict_tile.h"
 #include "evidence.h"
+#include "order_key.h"               // the keys k_predict_order (predict_order.inc) sorts
 
 namespace epx {
 
@@ -169,6 +170,7 @@ k_psis_rows(PsisRowsArgs a) {
 }
 
 #include "ppc.inc"                   // k_ppc, k_ppc_sites: posterior predictive checks, rows added up per draw
+#include "predict_order.inc"         // k_predict_order: order statistics across draws of new rows' f or replicated response
 #include "evidence_terms.inc"        // k_ev_terms: the terms of the bridge-sampling evidence estimate (evidence.hip)
 
 }  // namespace epx

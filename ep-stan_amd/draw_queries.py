@@ -1,16 +1,17 @@
-"""What `Master`'s draw queries -- mix_pred, mix_quantiles, predict, predict_new_group, loo, diagnostics and
-diagnostics(rank=True): everything answered from the tilted draws the last iteration left on the device -- share, away from
+"""What `Master`'s draw queries -- mix_pred, mix_quantiles, predict, predict_quantiles, predict_new_group, loo, diagnostics
+and diagnostics(rank=True): everything answered from the tilted draws the last iteration left on the device -- share, away from
 the class that runs EP.  Nothing here knows a `Master`:
 
   QUERIES, HostDraws, Queries   the eight engine methods behind the queries; the host route to each of them, stated once
                                 with `HipEngine`'s argument names and record shapes; and the per-method choice between an
                                 engine's own method and the host route
   CHECKS                        the engine method behind `Master.ppc`, on both routes and resolved by the same rule
+  INTERVALS                     the engine method behind `Master.predict_quantiles`, likewise
   gather_site_records           the ONLY way per-site records travel between ranks: one flat record per site, padded to the
                                 widest site; gather_named_records packs {name: array} records on top of it
   plan_rows                     predict's rows -> sites arithmetic, pure
-  sum_predict_rows, sum_loo_rows, merge_new_group
-                                the three row collectives, each with its own treatment of non-finite values
+  sum_predict_rows, sum_loo_rows, sum_order_rows, merge_new_group
+                                the four row collectives, each with its own treatment of non-finite values
 """
 
 import numpy as np
@@ -21,6 +22,7 @@ from . import loo as _loo
 from . import mix_pred as _mix_pred
 from . import newgroup as _newgroup
 from . import ppc as _ppc
+from . import predict_quantiles as _predict_quantiles
 from . import quantiles as _quantiles
 from . import site_params as _site_params
 
@@ -28,6 +30,8 @@ QUERIES = ('named_moments', 'pooled_count_pass', 'named_order_stats', 'predict',
            'draw_diagnostics', 'draw_rank_diagnostics')
 # the engine method behind `Master.ppc`: resolved like QUERIES, kept apart from the eight
 CHECKS = ('replicated_checks',)
+# the engine method behind `Master.predict_quantiles`: likewise
+INTERVALS = ('predict_order_stats',)
 
 
 class HostDraws(object):
@@ -81,6 +85,19 @@ class HostDraws(object):
                     None if row_group is None else row_group[lo:hi], None if y is None else y[lo:hi])
         return out
 
+    def predict_order_stats(self, Xn, row_lim, ranks, row_group=None, what='f', seed=0, row_id=None, with_n=False):
+        mid, gauss, _ = self.spec
+        _predict_quantiles.what_id(what, gauss)
+        out = np.zeros((Xn.shape[0], len(ranks)))
+        for j in range(self.K):                          # a site's draws are fetched where it has rows, one site at a time
+            lo, hi = int(row_lim[j]), int(row_lim[j + 1])
+            if hi > lo:
+                out[lo:hi] = _predict_quantiles.predict_order_stats_host(
+                    mid, self.D, self.site_ng[j:j + 1], gauss, [self.engine.get_draws(j, all_params=True)], Xn[lo:hi],
+                    [0, hi - lo], ranks, None if row_group is None else row_group[lo:hi], what, seed,
+                    np.arange(lo, hi, dtype=np.int64) if row_id is None else row_id[lo:hi])
+        return (out, int(self.engine.num_draws())) if with_n else out
+
     def predict_new_group(self, Xn, gidx, labels, y=None, seed=0, t0=0, R=1):
         mid, gauss, _ = self.spec
         phi = np.stack([np.ascontiguousarray(self.engine.get_draws(j)) for j in range(self.K)])
@@ -124,7 +141,7 @@ class HostDraws(object):
 
 
 class Queries(object):
-    """Answers each of QUERIES, at every call, from `host.engine` (the engine at that time) where it has a method of
+    """Answers each of QUERIES, CHECKS and INTERVALS, at every call, from `host.engine` (the engine at that time) where it has a method of
     that name and from `host` (a HostDraws over the same engine) where it has not: per method, since tests subclass both
     kinds of engine."""
 
@@ -132,7 +149,7 @@ class Queries(object):
         self.host = host
 
     def __getattr__(self, name):
-        if name not in QUERIES and name not in CHECKS:
+        if name not in QUERIES and name not in CHECKS and name not in INTERVALS:
             raise AttributeError(name)
         engine = self.host.engine
         return getattr(engine if hasattr(engine, name) else self.host, name)
@@ -379,6 +396,24 @@ def sum_loo_rows(comm, loc, lo, hi, N):
     both = comm.allreduce_sum(both)
     rec, code = both[:, :C], both[:, C:]
     return np.where(code == 1.0, np.nan, np.where(code == 2.0, np.inf, np.where(code == 3.0, -np.inf, rec)))
+
+
+def sum_order_rows(comm, loc, lo, hi, n):
+    """predict_quantiles' (n, T) order statistics on every rank from the rows [lo, hi) of this rank's sites: every rank's
+    rows in a zero-filled (n, T) array, one sum over the ranks.  NaN (a row with a NaN value) and +-inf (ordinary
+    values of an order statistic) travel as a code beside the values, as in `sum_loo_rows`; so does -0.0, whose sign a
+    sum with the other ranks' zeros would drop: every value arrives with the bits it had (a NaN as the default NaN)."""
+    if comm.world == 1:
+        return loc
+    T = loc.shape[1]
+    both = np.zeros((n, 2 * T))
+    both[lo:hi, :T] = np.where(np.isfinite(loc), loc, 0.0)
+    both[lo:hi, T:] = np.where(np.isnan(loc), 1.0, np.where(loc == np.inf, 2.0, np.where(loc == -np.inf, 3.0, np.where(
+        (loc == 0.0) & np.signbit(loc), 4.0, 0.0))))
+    both = comm.allreduce_sum(both) if n else both
+    rec, code = both[:, :T], both[:, T:]
+    return np.where(code == 1.0, np.nan, np.where(code == 2.0, np.inf, np.where(code == 3.0, -np.inf, np.where(
+        code == 4.0, -0.0, rec))))
 
 
 # ---- ppc

@@ -14,6 +14,7 @@ from . import diagnostics as _diagnostics
 from . import evidence as _evidence
 from . import loo as _loo
 from . import ppc as _ppc
+from . import predict_quantiles as _predict_quantiles
 from . import site_params as _site_params
 from ._lib import SamplerOpts, check, dptr
 
@@ -554,6 +555,36 @@ class HipEngine(object):
                                    row_group.ctypes.data_as(_lib.c_int32_p) if row_group is not None else None,
                                    dptr(Xn), dptr(y), dptr(theta), int(S), dptr(out), None))
         return out
+
+    def predict_order_stats(self, Xn, row_lim, ranks, row_group=None, what='f', seed=0, row_id=None, k0=0, count=None,
+                            theta=None, with_n=False):
+        """Order statistics across the draws of new rows (epx_predict_order_stats, include/epx.h): (n, len(ranks)) -- per
+        row v_(r) for the 0-based ranks r (ascending, distinct, below the draws per site, at most 32) of v = f (what =
+        'f') or of the replicated response f + sigma z (what = 'yrep', Gaussian family only), NaN for a row with a NaN
+        value.  Xn, row_lim, row_group: as `predict` takes them; seed: of the replicates' stream; row_id (n): the stream
+        index in [0, 2^32) of every row (None: its position in the call).  The draws are those of the last sampling
+        call, on the device; `theta` (count, S, P) injects draws instead (test hook).  with_n: also return the draws
+        per site."""
+        count = self.K - k0 if count is None else count
+        row_lim = np.ascontiguousarray(row_lim, dtype=np.int64)
+        if row_lim.shape != (count + 1,):
+            raise ValueError('row_lim: count + 1 = {} row limits'.format(count + 1))
+        Xn, row_group, _ = self._new_rows(Xn, int(row_lim[-1]), row_group, 'row_group', None)
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+        if row_id is not None:
+            row_id = np.ascontiguousarray(row_id, dtype=np.int64)
+            if row_id.shape != (Xn.shape[0],):
+                raise ValueError('row_id: one stream index per new row')
+        count, theta, S = self._draw_range(k0, count, theta)
+        out = np.zeros((Xn.shape[0], ranks.size))
+        n = ctypes.c_int()
+        check(self.lib.epx_predict_order_stats(
+            self.ctx, int(k0), int(count), row_lim.ctypes.data_as(_lib.c_int64_p),
+            row_group.ctypes.data_as(_lib.c_int32_p) if row_group is not None else None, dptr(Xn),
+            row_id.ctypes.data_as(_lib.c_int64_p) if row_id is not None else None,
+            _predict_quantiles.WHAT[what] if what in _predict_quantiles.WHAT else int(what), ctypes.c_uint64(int(seed)),
+            ranks.ctypes.data_as(_lib.c_int64_p), int(ranks.size), dptr(theta), int(S), dptr(out), ctypes.byref(n)))
+        return (out, n.value) if with_n else out
 
     def predict_new_group(self, Xn, gidx, labels, y=None, seed=0, t0=0, R=1, k0=0, count=None, theta=None):
         """Posterior predictive of groups that were not in the data (epx_predict_new_group, include/epx.h):

@@ -39,6 +39,7 @@ from . import evidence as _evidence
 from . import loo as _loo
 from . import newgroup as _newgroup
 from . import ppc as _ppc
+from . import predict_quantiles as _predict_quantiles
 from . import quantiles as _quantiles
 from . import reweight as _reweight
 from . import site_params as _site_params
@@ -838,6 +839,61 @@ class Master(object):
         out = np.empty_like(rec)
         out[rows] = rec
         return _dq.predictive_result(out, ys is not None, self.engine.num_draws())
+
+    def predict_quantiles(self, X_new, probs=(0.025, 0.25, 0.5, 0.75, 0.975), site_sizes=None, site_ind=None, j_ind=None,
+                          scale='mean', seed=0):
+        """Quantiles over the tilted draws of the last iteration of what the fitted site models predict for new rows:
+        the credible band of a row's regression line or fitted probability, and for the Gaussian family the predictive
+        interval of its response (include/epx.h, enum epx_pred_order, states the definition; the reference has no
+        counterpart: its user extracts every draw, re-applies alpha + x . beta and calls np.percentile).
+
+        X_new, site_sizes, site_ind, j_ind: the rows, as `predict` takes them; probs: probabilities in [0, 1]; scale:
+          'linear'    the linear predictor f = alpha + x . beta;
+          'mean'      what `predict`'s `mean` averages: sigmoid(f) for the Bernoulli-logit models, f for the Gaussian ones.
+                      The sigmoid is monotone, so the host maps the order statistics of f through it and interpolates:
+                      the type-7 quantile of sigmoid(f);
+          'response'  the replicated response f + sigma z, Gaussian family only (a ValueError otherwise: a 0/1 replicate
+                      has no useful quantile); seed: of the replicates' counter-based stream -- a replicate depends on
+                      (seed, the caller's row index, draw) only, so the result does not depend on `site_sizes` versus
+                      `site_ind` or on the number of ranks.
+
+        Returns a dict: `quantiles` (len(probs), n), the type-7 quantiles (NumPy's `linear`) in the caller's row order,
+        NaN for a row with a NaN value; `probs`; `scale`; `n` the draws per site.  The draws stay in device memory: the
+        kernel k_predict_order forms every row's values on the matrix pipe, sorts them on chip, and only the order
+        statistics the probabilities need leave the device (quantiles.rank_plan, quantiles.interpolate).  With several
+        ranks every rank computes the rows of its own sites and one all-reduce makes every rank return the same result."""
+        self._need_draws("predict quantiles", "nothing can be predicted from them")
+        if (site_sizes is None) == (site_ind is None):
+            raise ValueError("Give exactly one of `site_sizes` and `site_ind`")
+        if scale not in _predict_quantiles.SCALES:
+            raise ValueError("`scale`: one of {} (got {!r})".format(_predict_quantiles.SCALES, scale))
+        _, gauss, sg = self._site_spec()
+        if scale == 'response' and not gauss:
+            raise ValueError("scale='response' replicates the response: site model {!r} is Bernoulli-logit, whose 0/1 "
+                             "replicate has no useful quantile".format(self.model_name))
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+            raise ValueError("`seed`: an integer in [0, 2^64)")
+        X_new = _dq.new_rows(X_new, self.D)
+        n = X_new.shape[0]
+        if n >= 2 ** 32:
+            raise ValueError("{} rows: the replicates' stream counts rows below 2^32".format(n))
+        rows, lim, group = _dq.plan_rows(n, self.K, site_sizes, site_ind, j_ind, self._site_ng, sg, self.model_name)
+        S = self.engine.num_draws()
+        ranks, plan = _quantiles.rank_plan(S, probs)
+        in_order = site_sizes is not None                    # rows by site already: `rows` is 0 .. n - 1, nothing to gather
+        Xs = np.ascontiguousarray(X_new if in_order else X_new[rows])
+        lo, hi = int(lim[self.k_lo]), int(lim[self.k_hi])
+        local = self._queries.predict_order_stats(
+            Xs[lo:hi], lim[self.k_lo:self.k_hi + 1] - lo, ranks, None if group is None else group[lo:hi],
+            what='yrep' if scale == 'response' else 'f', seed=int(seed),
+            row_id=np.ascontiguousarray(rows[lo:hi], dtype=np.int64))
+        rec = _dq.sum_order_rows(self.comm, local, lo, hi, n)
+        stats = rec
+        if not in_order:
+            stats = np.empty_like(rec)
+            stats[rows] = rec
+        q = _predict_quantiles.quantiles_of(stats, ranks, plan, scale == 'mean' and not gauss)
+        return dict(quantiles=q, probs=np.atleast_1d(np.asarray(probs, dtype=np.float64)).copy(), scale=scale, n=int(S))
 
     def predict_new_group(self, X_new, group=None, y_new=None, R=1, seed=0):
         """Posterior predictive of rows of groups that were NOT in the data, from the tilted draws of the last iteration

@@ -41,15 +41,16 @@ def replicate_uniforms(seed, rows, S):
     return _newgroup.rng_u2(_newgroup.make_key(seed, 0), s, K_PPC, rows.astype(np.uint64)[None, :], 0)[0]
 
 
-def replicate_normals(seed, rows, S, dtype=np.float64):
-    """z (S, n) of the Gaussian family's replicates: csrc/epx_device.h rng_normal(key, s, K_PPC, e = row, 0) restated --
-    the Box-Muller pair of counter (s, K_PPC, e >> 1, 0), e the row as a 32-bit signed integer, cosine for even e.  The
-    uniforms are the stream's doubles; the logarithm, root, sine and cosine are taken in `dtype`."""
+def replicate_normals(seed, rows, S, dtype=np.float64, kind=K_PPC):
+    """z (S, n) of the Gaussian family's replicates: csrc/epx_device.h rng_normal(key, s, kind, e = row, 0) restated --
+    the Box-Muller pair of counter (s, kind, e >> 1, 0), e the row as a 32-bit signed integer, cosine for even e.  The
+    uniforms are the stream's doubles; the logarithm, root, sine and cosine are taken in `dtype`.  kind: K_PPC, or the
+    stream kind of another entry that replicates responses this way (predict_quantiles.K_PRED_REP)."""
     rows = _stream_rows(rows)
     e = rows.astype(np.uint32).view(np.int32)
     a = (e >> 1).astype(np.int64) & 0xFFFFFFFF
     s = np.arange(S, dtype=np.uint64)[:, None]
-    u1, u2 = _newgroup.rng_u2(_newgroup.make_key(seed, 0), s, K_PPC, a.astype(np.uint64)[None, :], 0)
+    u1, u2 = _newgroup.rng_u2(_newgroup.make_key(seed, 0), s, kind, a.astype(np.uint64)[None, :], 0)
     dt = np.dtype(dtype).type
     u1, u2 = u1.astype(dtype), u2.astype(dtype)
     rad = np.sqrt(dt(-2) * np.log(u1))

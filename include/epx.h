@@ -490,6 +490,49 @@ int epx_ppc(epx_ctx *ctx, int k0, int count, uint64_t seed, long long row0, cons
             double *out_groups /* groups x EPX_PC_COUNT */, double *out_sites /* count x EPX_PC_COUNT, may be NULL */,
             double *out_draws /* groups x 3 x S, may be NULL */, int *nsamp);
 
+/* Predictive intervals of NEW rows: order statistics across the draws of every row's linear predictor or replicated
+ * response (no counterpart in the reference, whose user calls `fit.extract`, re-applies alpha + x . beta by hand and calls
+ * np.percentile).  The definition, stated once; the kernel k_predict_order (csrc/predict_order.inc) and
+ * predict_quantiles.predict_order_stats_host both follow it.
+ * The new rows are described exactly as epx_predict takes them: sorted by site, those of site k0 + j are
+ * [row_lim[j], row_lim[j+1]), row_lim[0] = 0, n = row_lim[count]; row_group: 0-based group within the row's site (NULL:
+ * group 0 everywhere).  For row i of site k and draw s of that site, f_is is EPX_PR_F_MEAN's f = alpha_g(s) + x_i . beta_g(s),
+ * alpha and beta as EPX_NM_ALPHA / EPX_NM_BETA form them.  `what` selects the value v_is that is ordered:
+ *   EPX_PO_F     v_is = f_is; both families.
+ *   EPX_PO_YREP  v_is = f_is + sigma_s z, sigma_s = exp(phi_s[0]): the replicated response.  Gaussian family only; a
+ *                Bernoulli-logit model is an error that says so (a 0/1 replicate has no useful quantile).  z is built exactly
+ *                as epx_ppc builds its Gaussian replicate, at the stream kind 9 = K_PRED_REP, which no sampler uses: key
+ *                (seed, chain = 0), with (u1, u2) the uniforms of counter (s, K_PRED_REP, e >> 1, 0), e as a 32-bit signed
+ *                integer, z = sqrt(-2 log u1) cos(2 pi u2) for even e, ... sin ... for odd e.  e = row_id[i], the caller's
+ *                stream index of the row in [0, 2^32) (outside: an error); row_id == NULL: e = i, the row's position in the
+ *                call.  A replicate depends on (seed, row_id, s) only: not on the sites of the call, the row order, the
+ *                ranks or the grid.  EPX_PO_F checks row_id's range all the same and uses neither it nor seed.
+ * Per row the n_ranks order statistics v_(ranks[r]) of its S values: the draws ordered by the key of "Posterior quantiles"
+ * below, ranks ascending, distinct, in [0, S), between 1 and 32 (EPX_QT_MAX_RANKS).  A row with a NaN among its v_is has
+ * NaN at every rank, that row alone; +-inf are ordinary values.  out (host): n x n_ranks row-major, the caller's row order.
+ * The HOST interpolates (quantiles.rank_plan, quantiles.interpolate), as for epx_named_order_stats.
+ * theta == NULL: the draws of the last sampling call (error "no draws yet" before one, and an error when that call did not
+ * cover every site of the range), S is ignored; otherwise TEST HOOK: injected draws (count, S, P) row-major as
+ * epx_named_moments takes them.  nsamp out (may be NULL): draws per site.  At most D = 128 columns and 2^31 - 1 rows; n == 0
+ * returns without a launch.  A refusal launches nothing and writes nothing.
+ * Draw limit.  A workgroup takes work items of up to R rows of one (site, group), cut as epx_predict cuts its own, and sorts
+ * the item's keys in LDS, every row padded to N(S) = S rounded up to a power of two (at least 2) with the all-ones key.  R
+ * is the largest of 16, 8, 4, 2, 1 for which R x N(S) x 8 bytes fit the budget: 160 KiB - 1 KiB - the walk's fixed part (four
+ * coefficient slabs of 16 x (1 + D rounded up to 4) doubles, one per wave, each with 32 doubles of scales, and 8 doubles of
+ * NaN flags: 19 520 bytes at D = 32).  When not even
+ * R = 1 fits the call is an error that names S and the largest admissible S; there is no workspace fallback.  At D = 32:
+ * R = 16 up to S = 1024, at most S = 16384.  The environment variable EPX_PO_LDS_BYTES, read at every call, replaces the
+ * budget where it is smaller (tests reach R < 16 and the limit at small S with it; a value that is no whole non-negative
+ * number is ignored, and a refusal under a lowered budget names the variable); results do not depend on R.
+ * No floating-point atomics, no atomics at all, nothing merged across workgroups: a row's result has the same bits on every
+ * call, whatever the grid, the sub-range of sites or the other rows of the call.  Stream-ordered, one launch, one
+ * synchronisation. */
+enum epx_pred_order { EPX_PO_F = 0, EPX_PO_YREP = 1 };
+int epx_predict_order_stats(epx_ctx *ctx, int k0, int count, const int64_t *row_lim, const int32_t *row_group,
+                            const double *Xn, const int64_t *row_id /* n, or NULL */, int what, uint64_t seed,
+                            const int64_t *ranks, int n_ranks, const double *theta, int S,
+                            double *out /* n x n_ranks */, int *nsamp);
+
 /* The site normaliser of EP, log Z_k, by bridge sampling on the device (no counterpart in the reference, which has no
  * evidence estimate).  The definition, stated once; the kernels k_ev_fit / k_ev_bridge (csrc/evidence.hip), k_ev_terms
  * (csrc/evidence_terms.inc) and evidence.site_evidence_host all follow it.  What is estimated per site is log int exp(lq), lq the UNNORMALISED log
