@@ -83,15 +83,6 @@ int epx_model_dims(int model, int D, int *dphi, int *npar) {
 
 int epx_comm_allreduce_dev(epx_ctx *c, double *buf, size_t n, int op);      // epx_comm.hip
 
-template <typename K>
-static int set_lds(K kern, size_t bytes) {
-    if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return fail("hipFuncSetAttribute(%zu): %s", bytes, hipGetErrorString(e));
-    }
-    return 0;
-}
-
 // Queues one dense kernel (dense.hip) at dimension d: `grid` blocks of 256 threads, their work matrices in dynamic LDS or
 // in `buf`, grown to `nblocks` slots (epx_update.h: DensePlan).  d, ld and ws of the argument struct are filled here.
 template <typename Args>
@@ -100,10 +91,7 @@ static int launch_dense(void (*kern)(Args), int grid, hipStream_t stream, DevBuf
     HIPCHK(buf.grow(p.ws_doubles(nblocks)));            // (no doubles, no allocation, while the matrices are in LDS)
     a.d = d; a.ld = p.ld;
     a.ws.use_lds = p.in_lds; a.ws.global = p.in_lds ? nullptr : buf.p;
-    if (set_lds(kern, p.lds_bytes)) return -1;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), p.lds_bytes, stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch(kern, dim3(grid), dim3(256), p.lds_bytes, stream, a);
 }
 
 // A caller's array that may only be read goes up to the device; one that may be written is filled from it.
@@ -187,7 +175,8 @@ static int ctx_create(int device, int model, int K_local, int D, const int64_t *
     c->pg = model == EPX_M1B_SG ? 1 : 1 + D;
     c->multi = g_cnt != nullptr;
     c->ng_max = 1; c->nt_max = 1;
-    std::vector<int> g0((size_t)K_local + 1, 0);
+    std::vector<int> &g0 = c->site_g0;
+    g0.assign((size_t)K_local + 1, 0);
     {
         int64_t gi = 0;
         for (int k = 0; k < K_local; ++k) {
@@ -1277,8 +1266,7 @@ int epx_named_moments(epx_ctx *c, int k0, int count, const int32_t *names, int n
     const size_t nout = (size_t)count * a.L;
     HIPCHK(c->named_out.grow(2 * nout));
     a.mean = c->named_out; a.m2 = c->named_out + nout;
-    hipLaunchKernelGGL(k_named_moments, dim3(count), dim3(256), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    if (launch(k_named_moments, dim3(count), dim3(256), 0, c->stream, a)) return -1;
     HIPCHK(hipMemcpyAsync(mean, a.mean, nout * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(m2, a.m2, nout * 8, hipMemcpyDeviceToHost, c->stream));
     if (nsamp) *nsamp = src.S;
@@ -1290,8 +1278,7 @@ int epx_named_order_stats(epx_ctx *c, int k0, int count, const int32_t *names, i
     CTX(c);
     if (check_range(c, k0, count)) return -1;
     if (!out) return fail("epx_named_order_stats: out is required");
-    if (!ranks || n_ranks < 1 || n_ranks > EPX_QT_MAX_RANKS)
-        return fail("epx_named_order_stats: between 1 and %d ranks (got %d)", (int)EPX_QT_MAX_RANKS, n_ranks);
+    if (check_rank_count("epx_named_order_stats", ranks, n_ranks)) return -1;
     OrderArgs a;
     DrawSource src;
     if (named_front(c, "epx_named_order_stats", k0, count, names, n_names, theta, S, c->ng_max, a.nm, &src)) return -1;
@@ -1299,25 +1286,17 @@ int epx_named_order_stats(epx_ctx *c, int k0, int count, const int32_t *names, i
     if (S > order_max_draws())
         return fail("epx_named_order_stats: S = %d draws per site, at most %d (a site's keys, padded to a power of two, are "
                     "sorted in LDS)", S, order_max_draws());
-    for (int i = 0; i < n_ranks; ++i) {
-        if (ranks[i] < 0 || ranks[i] >= S)
-            return fail("epx_named_order_stats: rank %lld outside [0, %d), the draws per site", (long long)ranks[i], S);
-        if (i > 0 && ranks[i] <= ranks[i - 1]) return fail("epx_named_order_stats: the ranks have to be ascending and distinct");
-    }
+    if (fill_ranks("epx_named_order_stats", ranks, n_ranks, S, a.rank)) return -1;
     if ((long long)count * a.nm.L > 0x7fffffffLL)
         return fail("epx_named_order_stats: %d sites x %d elements in one call, at most 2^31 - 1", count, a.nm.L);
     a.n_ranks = n_ranks;
-    for (int i = 0; i < EPX_QT_MAX_RANKS; ++i) a.rank[i] = i < n_ranks ? (int)ranks[i] : 0;
-    a.npad = 2;
-    while (a.npad < S) a.npad *= 2;
+    a.npad = pow2_pad(S);
     const size_t lds = (size_t)a.npad * 8, nout = (size_t)count * a.nm.L * n_ranks;
     StreamSync sync{c->stream};
     if (upload_draws(c, src, &a.nm.draws)) return -1;
-    if (set_lds(k_site_order_stats, lds)) return -1;
     HIPCHK(c->order_out.grow(nout));
     a.out = c->order_out;
-    hipLaunchKernelGGL(k_site_order_stats, dim3((unsigned)(count * a.nm.L)), dim3(EPX_QT_THREADS), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
+    if (launch(k_site_order_stats, dim3((unsigned)(count * a.nm.L)), dim3(EPX_QT_THREADS), lds, c->stream, a)) return -1;
     HIPCHK(hipMemcpyAsync(out, a.out, nout * 8, hipMemcpyDeviceToHost, c->stream));
     if (nsamp) *nsamp = S;
     return sync.finish();
@@ -1372,9 +1351,7 @@ int epx_pooled_count_pass(epx_ctx *c, int k0, int count, const int32_t *names, i
     HIPCHK(hipMemsetAsync(a.hist, 0, (n_hist + L) * 8, c->stream));
     if (shift < 56) HIPCHK(hipMemcpyAsync(prefix_d, prefix, L * nt * 8, hipMemcpyHostToDevice, c->stream));
     a.prefix = prefix_d;
-    if (set_lds(k_pooled_count, lds)) return -1;
-    hipLaunchKernelGGL(k_pooled_count, dim3((unsigned)ntile, (unsigned)nslab), dim3(EPX_QT_THREADS), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
+    if (launch(k_pooled_count, dim3((unsigned)ntile, (unsigned)nslab), dim3(EPX_QT_THREADS), lds, c->stream, a)) return -1;
     static_assert(sizeof(long long) == sizeof(unsigned long long), "counts are copied as they are");
     HIPCHK(hipMemcpyAsync(hist, a.hist, n_hist * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(n_nan, a.n_nan, L * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1387,11 +1364,10 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
     CTX(c);
     if (check_range(c, k0, count)) return -1;
     if (!row_lim) return fail("epx_predict: row_lim is required");
-    if (c->D > EPX_PR_DMAX) return fail("epx_predict: D = %d columns, at most %d", c->D, (int)EPX_PR_DMAX);
+    if (check_walk_columns(c, "epx_predict")) return -1;
     int64_t n;
     if (new_row_count("epx_predict", k0, count, row_lim, &n)) return -1;
     const size_t D = c->D;
-    PredictArgs a;
     DrawSource src;
     if (draw_source(c, "epx_predict", k0, count, theta, S, nullptr, &src)) return -1;
     if (nsamp) *nsamp = src.S;
@@ -1404,22 +1380,18 @@ int epx_predict(epx_ctx *c, int k0, int count, const int64_t *row_lim, const int
     std::vector<int> perm((size_t)n);
     std::vector<PredictWg> wg;
     if (cut_new_rows(c, "epx_predict", k0, count, row_lim, row_group, EPX_PR_WG_ROWS, perm.data(), wg)) return -1;
-    a.m = predict_model(c); a.S = src.S;
-    a.k0 = k0; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    PredictArgs a = bind_walk(c, k0, src.S);
     const size_t nn = (size_t)n, nwg = wg.size();
     HIPCHK(c->pred_ws.grow(nn * D + nn + nn * EPX_PR_COUNT));
     HIPCHK(c->pred_iws.grow(4 * nwg + nn));
     double *X_d = c->pred_ws, *y_d = X_d + nn * D, *out_d = y_d + nn;
     int *wg_d = c->pred_iws, *perm_d = wg_d + 4 * nwg;
-    static_assert(sizeof(PredictWg) == 4 * sizeof(int), "PredictWg is four ints");
     StreamSync sync{c->stream};          // (`perm` and `wg` are this frame's: the guard is declared behind them)
     if (upload_draws(c, src, &a.draws)) return -1;
     if (queue_new_rows(c, nn, Xn, yn, perm.data(), X_d, y_d, perm_d)) return -1;
-    HIPCHK(hipMemcpyAsync(wg_d, wg.data(), nwg * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream));
-    a.wg = reinterpret_cast<const PredictWg *>(wg_d); a.perm = perm_d;
-    a.X = X_d; a.y = yn ? y_d : nullptr; a.out = out_d;
-    hipLaunchKernelGGL(k_predict, dim3((unsigned)nwg), dim3(256), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    if (upload_items(c, wg, wg_d, &a.wg)) return -1;
+    a.perm = perm_d; a.X = X_d; a.y = yn ? y_d : nullptr; a.out = out_d;
+    if (launch(k_predict, dim3((unsigned)nwg), dim3(256), 0, c->stream, a)) return -1;
     HIPCHK(hipMemcpyAsync(out, out_d, nn * EPX_PR_COUNT * 8, hipMemcpyDeviceToHost, c->stream));
     return sync.finish();
 }
@@ -1430,7 +1402,7 @@ int epx_predict_order_stats(epx_ctx *c, int k0, int count, const int64_t *row_li
     CTX(c);
     const char *who = "epx_predict_order_stats";
     if (check_range(c, k0, count)) return -1;
-    if (c->D > EPX_PR_DMAX) return fail("%s: D = %d columns, at most %d", who, c->D, (int)EPX_PR_DMAX);
+    if (check_walk_columns(c, who)) return -1;
     int64_t n;
     if (new_row_count(who, k0, count, row_lim, &n)) return -1;
     if (what != EPX_PO_F && what != EPX_PO_YREP)
@@ -1438,8 +1410,7 @@ int epx_predict_order_stats(epx_ctx *c, int k0, int count, const int64_t *row_li
     if (what == EPX_PO_YREP && !c->gauss)
         return fail("%s: EPX_PO_YREP is defined for the Gaussian family only: a Bernoulli-logit model's 0/1 replicate has no "
                     "useful quantile", who);
-    if (!ranks || n_ranks < 1 || n_ranks > EPX_QT_MAX_RANKS)
-        return fail("%s: between 1 and %d ranks (got %d)", who, (int)EPX_QT_MAX_RANKS, n_ranks);
+    if (check_rank_count(who, ranks, n_ranks)) return -1;
     if (n > 0 && (!Xn || !out)) return fail("%s: Xn and out are required", who);
     const size_t nn = (size_t)n, D = c->D;
     std::vector<uint32_t> ids;
@@ -1456,23 +1427,11 @@ int epx_predict_order_stats(epx_ctx *c, int k0, int count, const int64_t *row_li
     DrawSource src;
     if (draw_source(c, who, k0, count, theta, S, nullptr, &src)) return -1;
     S = src.S;
-    for (int i = 0; i < n_ranks; ++i) {
-        if (ranks[i] < 0 || ranks[i] >= S)
-            return fail("%s: rank %lld outside [0, %d), the draws per site", who, (long long)ranks[i], S);
-        if (i > 0 && ranks[i] <= ranks[i - 1]) return fail("%s: the ranks have to be ascending and distinct", who);
-    }
-    a.p.m = predict_model(c); a.p.S = S;
+    if (fill_ranks(who, ranks, n_ranks, S, a.rank)) return -1;
+    a.p = bind_walk(c, k0, S);
     // the keys' share of the LDS: R rows of N(S) keys behind the walk's fixed part
-    size_t budget = pred_order_budget(a.p.m.KP);
     std::string lowered;                                  // what a refusal says of the variable, where it lowered the budget
-    if (const char *e = getenv("EPX_PO_LDS_BYTES")) {     // (a value that is no whole non-negative number is ignored)
-        char *end = nullptr;
-        const long long v = strtoll(e, &end, 10);
-        if (end != e && *end == '\0' && v >= 0 && (size_t)v < budget) {
-            budget = (size_t)v;
-            lowered = std::string("; EPX_PO_LDS_BYTES = ") + e + " lowers the keys' budget";
-        }
-    }
+    const size_t budget = lds_budget("EPX_PO_LDS_BYTES", pred_order_budget(a.p.m.KP), &lowered);
     size_t nmax = 0;                                      // the largest power of two of keys that fits: the largest S
     for (size_t m = 1; m * 8 <= budget; m *= 2) nmax = m;
     const auto too_many = [&](size_t most) {
@@ -1480,8 +1439,7 @@ int epx_predict_order_stats(epx_ctx *c, int k0, int count, const int64_t *row_li
                     (int)most, lowered.c_str());
     };
     if ((size_t)S > nmax) return too_many(nmax);
-    a.npad = 2; a.lg = 1;
-    while (a.npad < S) { a.npad *= 2; ++a.lg; }
+    a.npad = pow2_pad(S, &a.lg);
     int R = 16;
     while (R > 1 && (size_t)R * a.npad * 8 > budget) R /= 2;
     if ((size_t)R * a.npad * 8 > budget) return too_many(0);      // (S = 1 under a budget below two keys)
@@ -1492,9 +1450,7 @@ int epx_predict_order_stats(epx_ctx *c, int k0, int count, const int64_t *row_li
     if (wg.size() > 0x7fffffff) return fail("%s: %lld work items in one call, at most 2^31 - 1", who, (long long)wg.size());
     if (nsamp) *nsamp = S;                                // (behind the last refusal: a refusal writes nothing)
     if (n == 0) return 0;
-    a.p.k0 = k0; a.p.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
     a.what = what; a.seed = seed; a.n_ranks = n_ranks;
-    for (int i = 0; i < EPX_QT_MAX_RANKS; ++i) a.rank[i] = i < n_ranks ? (int)ranks[i] : 0;
     const size_t nwg = wg.size(), lds = pred_order_fixed_bytes(a.p.m.KP) + (size_t)R * a.npad * 8;
     a.nwg = (int)nwg;
     HIPCHK(c->pred_ws.grow(nn * D + nn * n_ranks));
@@ -1502,19 +1458,16 @@ int epx_predict_order_stats(epx_ctx *c, int k0, int count, const int64_t *row_li
     double *X_d = c->pred_ws, *out_d = X_d + nn * D;
     int *wg_d = c->pred_iws, *perm_d = wg_d + 4 * nwg, *id_d = perm_d + nn;
     static_assert(sizeof(uint32_t) == sizeof(int), "the rows' stream indices lie in the int workspace");
-    if (set_lds(k_predict_order, lds)) return -1;
     StreamSync sync{c->stream};          // (`ids`, `perm` and `wg` are this frame's: the guard is declared behind them)
     if (upload_draws(c, src, &a.p.draws)) return -1;
     if (queue_new_rows(c, nn, Xn, nullptr, perm.data(), X_d, nullptr, perm_d)) return -1;
-    HIPCHK(hipMemcpyAsync(wg_d, wg.data(), nwg * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream));
+    if (upload_items(c, wg, wg_d, &a.p.wg)) return -1;
     if (!ids.empty()) HIPCHK(hipMemcpyAsync(id_d, ids.data(), nn * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    a.p.wg = reinterpret_cast<const PredictWg *>(wg_d); a.p.perm = perm_d;
-    a.p.X = X_d; a.p.y = nullptr; a.p.out = nullptr;
+    a.p.perm = perm_d; a.p.X = X_d;
     a.row_id = ids.empty() ? nullptr : reinterpret_cast<const uint32_t *>(id_d);
     a.out = out_d;
     // (the kernel's registers leave room for two workgroups per compute unit, the LDS for one where the keys fill it)
-    hipLaunchKernelGGL(k_predict_order, dim3(walk_grid(c, nwg, 2 * lds <= LDS_CAP ? 2 : 1)), dim3(256), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
+    if (launch(k_predict_order, dim3(walk_grid(c, nwg, 2 * lds <= LDS_CAP ? 2 : 1)), dim3(256), lds, c->stream, a)) return -1;
     HIPCHK(hipMemcpyAsync(out, out_d, nn * n_ranks * 8, hipMemcpyDeviceToHost, c->stream));
     return sync.finish();
 }
@@ -1526,7 +1479,7 @@ int epx_predict_new_group(epx_ctx *c, int k0, int count, uint64_t seed, long lon
     const char *who = "epx_predict_new_group";
     if (check_range(c, k0, count)) return -1;
     if (R < 1 || R > EPX_NGP_RMAX) return fail("%s: R must be in 1..%d (got %d)", who, (int)EPX_NGP_RMAX, R);
-    if (c->D > EPX_PR_DMAX) return fail("%s: D = %d columns, at most %d", who, c->D, (int)EPX_PR_DMAX);
+    if (check_walk_columns(c, who)) return -1;
     if (n < 0 || n > 0x7fffffff) return fail("%s: %lld rows in one call, between 0 and 2^31 - 1", who, n);
     if (G < 0 || (G > 0 && !group_label)) return fail("%s: G = %d groups need their labels", who, G);
     if (t0 < 0 || t0 > (1ll << 32)) return fail("%s: t0 = %lld outside [0,2^32]", who, t0);
@@ -1574,11 +1527,9 @@ int epx_predict_new_group(epx_ctx *c, int k0, int count, uint64_t seed, long lon
     a.perm = perm_d; a.gfirst = gfirst_d; a.label = label_d; a.live = live_d;
     a.X = X_d; a.y = yn ? y_d : nullptr;
     a.part_rows = rows_d; a.part_grp = grp_d; a.out = out_d; a.out_group = outg_d;
-    hipLaunchKernelGGL(k_newgroup, dim3(walk_grid(c, (size_t)a.nitem, 4)), dim3(256), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    if (launch(k_newgroup, dim3(walk_grid(c, (size_t)a.nitem, 4)), dim3(256), 0, c->stream, a)) return -1;
     const long long mblocks = ((long long)n + G + 255) / 256;
-    hipLaunchKernelGGL(k_newgroup_merge, dim3((unsigned)(mblocks < 65536 ? mblocks : 65536)), dim3(256), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    if (launch(k_newgroup_merge, dim3((unsigned)(mblocks < 65536 ? mblocks : 65536)), dim3(256), 0, c->stream, a)) return -1;
     HIPCHK(hipMemcpyAsync(out, out_d, nn * EPX_PR_COUNT * 8, hipMemcpyDeviceToHost, c->stream));
     if (out_group) HIPCHK(hipMemcpyAsync(out_group, outg_d, nG * EPX_NG_COUNT * 8, hipMemcpyDeviceToHost, c->stream));
     return sync.finish();
@@ -1590,26 +1541,19 @@ static size_t psis_lds_bytes(int M) { return (size_t)16 * psis_scratch_doubles(M
 int epx_loo(epx_ctx *c, int k0, int count, const double *theta, int S, double *out, int *nsamp) {
     CTX(c);
     if (check_range(c, k0, count)) return -1;
-    if (c->D > EPX_PR_DMAX) return fail("epx_loo: D = %d columns, at most %d", c->D, (int)EPX_PR_DMAX);
+    if (check_walk_columns(c, "epx_loo")) return -1;
     if (!out) return fail("epx_loo: out is required");
     LooArgs a;
     DrawSource src;
     if (draw_source(c, "epx_loo", k0, count, theta, S, nullptr, &src)) return -1;
     S = src.S;
-    if (nsamp) *nsamp = S;
-    a.p.m = predict_model(c); a.p.S = S;
-    a.p.k0 = k0; a.p.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
-    a.p.perm = nullptr; a.p.y = nullptr; a.p.out = nullptr; a.p.X = c->X;
-    a.y8 = c->y; a.yd = c->yd;
+    a.p = bind_walk(c, k0, S);
+    a.p.X = c->X; a.y8 = c->y; a.yd = c->yd;
     a.M = psis_tail_length(S); a.mfit = psis_fit_points(a.M);
     a.stride = loo_stride(S);
     // LDS: [coefficient slab | log sigma, sigma of the slab | PSIS scratch | tiles]; the tiles go to the workspace when
     // not even one fits
-    size_t cap = LDS_CAP - 1024;
-    if (const char *e = getenv("EPX_LOO_LDS_BYTES")) {
-        const long long v = atoll(e);
-        if (v >= 0 && (size_t)v < cap) cap = (size_t)v;
-    }
+    const size_t cap = lds_budget("EPX_LOO_LDS_BYTES", LDS_CAP - 1024);
     const size_t fixed = ((size_t)a.p.m.KP * 16 + 32) * 8 + psis_lds_bytes(a.M), tile = (size_t)16 * a.stride * 8;
     if (a.mfit > PSIS_FIT_MAX || fixed > LDS_CAP - 1024)
         return fail("epx_loo: S = %d draws: the tail of %d draws per row does not fit the LDS", S, a.M);
@@ -1619,18 +1563,10 @@ int epx_loo(epx_ctx *c, int k0, int count, const double *theta, int S, double *o
     const size_t lds = fixed + (in_lds ? a.tiles * tile : 0);
     // work items: up to 16 x tiles rows of one (site, group), in the context's row order
     const int item = 16 * a.tiles;
+    if (check_ctx_rows(c, "epx_loo")) return -1;
+    if (nsamp) *nsamp = S;                                // (behind the last refusal: a refusal writes nothing)
     std::vector<PredictWg> wg;
-    for (int j = 0; j < count; ++j) {
-        const int k = k0 + j, ng = c->multi ? c->g_cnt[k] : 1;
-        size_t gi = 0;
-        if (c->multi) for (int i = 0; i < k; ++i) gi += (size_t)c->g_cnt[i];
-        for (int g = 0; g < ng; ++g) {
-            const int64_t lo = c->multi ? c->g_lim[gi + g] : c->k_lim[k], hi = c->multi ? c->g_lim[gi + g + 1] : c->k_lim[k + 1];
-            for (int64_t r = lo; r < hi; r += item)
-                wg.push_back(PredictWg{j, g, (int)r, (int)(hi - r < item ? hi - r : item)});
-        }
-    }
-    if (c->N > 0x7fffffff) return fail("epx_loo: %lld rows, at most 2^31 - 1", (long long)c->N);
+    cut_ctx_rows(c, k0, count, item, wg);
     a.row0 = c->k_lim[k0];
     const size_t rows = (size_t)(c->k_lim[k0 + count] - c->k_lim[k0]), nwg = wg.size();
     const unsigned grid = walk_grid(c, nwg, in_lds ? 4 : 2);       // (the LDS holds one or two workgroups per compute unit)
@@ -1639,14 +1575,10 @@ int epx_loo(epx_ctx *c, int k0, int count, const double *theta, int S, double *o
     HIPCHK(c->pred_iws.grow(4 * nwg));
     a.out = c->loo_ws; a.slab = in_lds ? nullptr : c->loo_ws + n_out;
     a.nwg = (int)nwg;
-    int *wg_d = c->pred_iws;
-    if (set_lds(k_loo, lds)) return -1;
     StreamSync sync{c->stream};          // (`wg` is this frame's: the guard is declared behind it)
     if (upload_draws(c, src, &a.p.draws)) return -1;
-    HIPCHK(hipMemcpyAsync(wg_d, wg.data(), nwg * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream));
-    a.p.wg = reinterpret_cast<const PredictWg *>(wg_d);
-    hipLaunchKernelGGL(k_loo, dim3(grid), dim3(256), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
+    if (upload_items(c, wg, c->pred_iws, &a.p.wg)) return -1;
+    if (launch(k_loo, dim3(grid), dim3(256), lds, c->stream, a)) return -1;
     HIPCHK(hipMemcpyAsync(out, a.out, n_out * 8, hipMemcpyDeviceToHost, c->stream));
     return sync.finish();
 }
@@ -1655,9 +1587,9 @@ int epx_ppc(epx_ctx *c, int k0, int count, uint64_t seed, long long row0, const 
             double *out_sites, double *out_draws, int *nsamp) {
     CTX(c);
     if (check_range(c, k0, count)) return -1;
-    if (c->D > EPX_PR_DMAX) return fail("epx_ppc: D = %d columns, at most %d", c->D, (int)EPX_PR_DMAX);
+    if (check_walk_columns(c, "epx_ppc")) return -1;
     if (!out_groups) return fail("epx_ppc: out_groups is required");
-    if (c->N > 0x7fffffff) return fail("epx_ppc: %lld rows, at most 2^31 - 1", (long long)c->N);
+    if (check_ctx_rows(c, "epx_ppc")) return -1;
     if (row0 < 0 || row0 + (long long)c->k_lim[k0 + count] >= (1ll << 32))
         return fail("epx_ppc: row0 = %lld puts the rows of the call at [%lld,%lld), outside [0,2^32 - 1)", row0,
                     row0 + (long long)c->k_lim[k0], row0 + (long long)c->k_lim[k0 + count]);
@@ -1665,29 +1597,17 @@ int epx_ppc(epx_ctx *c, int k0, int count, uint64_t seed, long long row0, const 
     DrawSource src;
     if (draw_source(c, "epx_ppc", k0, count, theta, S, nullptr, &src)) return -1;
     S = src.S;
-    if (nsamp) *nsamp = S;
-    a.p.m = predict_model(c); a.p.S = S;
+    a.p = bind_walk(c, k0, S);
     if (S > ppc_max_draws(a.p.m.KP))
         return fail("epx_ppc: S = %d draws, at most %d (a group's 3 x S per-draw sums are kept in LDS)", S,
                     ppc_max_draws(a.p.m.KP));
-    a.p.k0 = k0; a.p.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
-    a.p.perm = nullptr; a.p.y = nullptr; a.p.out = nullptr; a.p.X = c->X;
-    a.y8 = c->y; a.yd = c->yd;
+    if (nsamp) *nsamp = S;                                // (behind the last refusal: a refusal writes nothing)
+    a.p.X = c->X; a.y8 = c->y; a.yd = c->yd;
     a.seed = seed; a.row0 = row0; a.count = count;
-    // work items: the groups of the range, in the context's order; site_first: the first of every site
+    // work items: the groups of the range, whole, in the context's order; site_first: the first of every site
     std::vector<PredictWg> wg;
-    std::vector<int> site_first((size_t)count + 1, 0);
-    size_t gi = 0;
-    if (c->multi) for (int i = 0; i < k0; ++i) gi += (size_t)c->g_cnt[i];
-    for (int j = 0; j < count; ++j) {
-        const int k = k0 + j, ng = c->multi ? c->g_cnt[k] : 1;
-        for (int g = 0; g < ng; ++g) {
-            const int64_t lo = c->multi ? c->g_lim[gi + g] : c->k_lim[k], hi = c->multi ? c->g_lim[gi + g + 1] : c->k_lim[k + 1];
-            wg.push_back(PredictWg{j, g, (int)lo, (int)(hi - lo)});
-        }
-        gi += (size_t)ng;
-        site_first[(size_t)j + 1] = (int)wg.size();
-    }
+    std::vector<int> site_first;
+    cut_ctx_rows(c, k0, count, 0, wg, &site_first);
     const size_t ng_all = wg.size(), n_draws = ng_all * 3 * (size_t)S, n_grp = ng_all * EPX_PC_COUNT,
                  n_site = (size_t)count * EPX_PC_COUNT, lds = ppc_lds_bytes(a.p.m.KP, S);
     a.ngroups = (int)ng_all;
@@ -1695,16 +1615,13 @@ int epx_ppc(epx_ctx *c, int k0, int count, uint64_t seed, long long row0, const 
     HIPCHK(c->pred_iws.grow(4 * ng_all + site_first.size()));
     a.per_draw = c->ppc_ws; a.out_groups = a.per_draw + n_draws; a.out_sites = a.out_groups + n_grp;
     int *wg_d = c->pred_iws, *first_d = wg_d + 4 * ng_all;
-    if (set_lds(k_ppc, lds)) return -1;
     StreamSync sync{c->stream};          // (`wg` and `site_first` are this frame's: the guard is declared behind them)
     if (upload_draws(c, src, &a.p.draws)) return -1;
-    HIPCHK(hipMemcpyAsync(wg_d, wg.data(), ng_all * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream));
+    if (upload_items(c, wg, wg_d, &a.p.wg)) return -1;
     HIPCHK(hipMemcpyAsync(first_d, site_first.data(), site_first.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    a.p.wg = reinterpret_cast<const PredictWg *>(wg_d); a.site_first = first_d;
-    hipLaunchKernelGGL(k_ppc, dim3(walk_grid(c, ng_all, 4)), dim3(256), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_ppc_sites, dim3((unsigned)((count + 15) / 16)), dim3(256), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    a.site_first = first_d;
+    if (launch(k_ppc, dim3(walk_grid(c, ng_all, 4)), dim3(256), lds, c->stream, a)) return -1;
+    if (launch(k_ppc_sites, dim3((unsigned)((count + 15) / 16)), dim3(256), 0, c->stream, a)) return -1;
     HIPCHK(hipMemcpyAsync(out_groups, a.out_groups, n_grp * 8, hipMemcpyDeviceToHost, c->stream));
     if (out_sites) HIPCHK(hipMemcpyAsync(out_sites, a.out_sites, n_site * 8, hipMemcpyDeviceToHost, c->stream));
     if (out_draws) HIPCHK(hipMemcpyAsync(out_draws, a.per_draw, n_draws * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1715,9 +1632,9 @@ int epx_site_evidence(epx_ctx *c, int k0, int count, uint64_t seed, long long si
                       double *out, double *out_terms, double *elapsed_ms) {
     CTX(c);
     if (check_range(c, k0, count)) return -1;
-    if (c->D > EPX_PR_DMAX) return fail("epx_site_evidence: D = %d columns, at most %d", c->D, (int)EPX_PR_DMAX);
+    if (check_walk_columns(c, "epx_site_evidence")) return -1;
     if (!out) return fail("epx_site_evidence: out is required");
-    if (c->N > 0x7fffffff) return fail("epx_site_evidence: %lld rows, at most 2^31 - 1", (long long)c->N);
+    if (check_ctx_rows(c, "epx_site_evidence")) return -1;
     if (site0 < 0 || site0 + (long long)c->K >= (1ll << 31))
         return fail("epx_site_evidence: site0 = %lld puts the context's %d sites outside [0,2^31)", site0, c->K);
     EvidenceArgs a;
@@ -1745,24 +1662,14 @@ int epx_site_evidence(epx_ctx *c, int k0, int count, uint64_t seed, long long si
         return fail("epx_site_evidence: N1 = %d estimation draws: the terms of the bridge (%zu bytes) do not fit the LDS",
                     a.N1, lds_bridge);
     a.k0 = k0; a.pg = c->model == EPX_M1B_SG ? 1 : 1 + c->D;
-    a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    a.site_g0 = site_g0(c);
     a.X = c->X; a.y8 = c->y; a.yd = c->yd;
     a.cav_Om = c->cav_Om; a.cav_mu = c->cav_mu;
     a.seed = seed; a.site0 = site0;
-    // the groups of the range, in the context's order; site_first: the first of every site
+    // the groups of the range, whole, in the context's order; site_first: the first of every site
     std::vector<PredictWg> wg;
-    std::vector<int> site_first((size_t)count + 1, 0);
-    size_t gi = 0;
-    if (c->multi) for (int i = 0; i < k0; ++i) gi += (size_t)c->g_cnt[i];
-    for (int j = 0; j < count; ++j) {
-        const int k = k0 + j, ng = c->multi ? c->g_cnt[k] : 1;
-        for (int g = 0; g < ng; ++g) {
-            const int64_t lo = c->multi ? c->g_lim[gi + g] : c->k_lim[k], hi = c->multi ? c->g_lim[gi + g + 1] : c->k_lim[k + 1];
-            wg.push_back(PredictWg{j, g, (int)lo, (int)(hi - lo)});
-        }
-        gi += (size_t)ng;
-        site_first[(size_t)j + 1] = (int)wg.size();
-    }
+    std::vector<int> site_first;
+    cut_ctx_rows(c, k0, count, 0, wg, &site_first);
     const size_t ng_all = wg.size(), fitw = evidence_fit_doubles(P), n_fit = (size_t)count * fitw,
                  n_terms = (size_t)count * 2 * a.N1, n_out = (size_t)count * EPX_EV_COUNT,
                  n_prop = out_terms ? (size_t)count * a.N1 * P : 0;
@@ -1771,19 +1678,16 @@ int epx_site_evidence(epx_ctx *c, int k0, int count, uint64_t seed, long long si
     a.fit = c->ev_ws; a.terms = a.fit + n_fit; a.out = a.terms + n_terms; a.prop = out_terms ? a.out + n_out : nullptr;
     int *wg_d = c->pred_iws, *first_d = wg_d + 4 * ng_all;
     const size_t lds_fit = (evidence_packed(P) + 2 * P + 2) * 8, lds_terms = evidence_terms_doubles(P, a.m.KP) * 8;
-    if (set_lds(k_ev_fit, lds_fit) || set_lds(k_ev_terms, lds_terms) || set_lds(k_ev_bridge, lds_bridge)) return -1;
     StreamSync sync{c->stream};          // (`wg` and `site_first` are this frame's: the guard is declared behind them)
     if (upload_draws(c, src, &a.draws)) return -1;
-    HIPCHK(hipMemcpyAsync(wg_d, wg.data(), ng_all * sizeof(PredictWg), hipMemcpyHostToDevice, c->stream));
+    if (upload_items(c, wg, wg_d, &a.wg)) return -1;
     HIPCHK(hipMemcpyAsync(first_d, site_first.data(), site_first.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    a.wg = reinterpret_cast<const PredictWg *>(wg_d); a.site_first = first_d;
+    a.site_first = first_d;
     HIPCHK(hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(k_ev_fit, dim3((unsigned)count), dim3(256), lds_fit, c->stream, a);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_ev_terms, dim3((unsigned)count), dim3(256), lds_terms, c->stream, a);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_ev_bridge, dim3((unsigned)count), dim3(256), lds_bridge, c->stream, a);
-    HIPCHK(hipGetLastError());
+    const dim3 sites((unsigned)count), threads(256);
+    if (launch(k_ev_fit, sites, threads, lds_fit, c->stream, a) || launch(k_ev_terms, sites, threads, lds_terms, c->stream, a) ||
+        launch(k_ev_bridge, sites, threads, lds_bridge, c->stream, a))
+        return -1;
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     HIPCHK(hipMemcpyAsync(out, a.out, n_out * 8, hipMemcpyDeviceToHost, c->stream));
     if (out_terms) {
@@ -1813,20 +1717,18 @@ int epx_draw_diagnostics(epx_ctx *c, int k0, int count, const double *theta, int
     if (draw_source(c, "epx_draw_diagnostics", k0, count, theta, S, &chains, &src)) return -1;
     S = src.S; chains = src.chains;
     a.k0 = k0; a.chains = chains; a.nkeep = S / chains; a.P = c->P;
-    a.d = c->d; a.pg = c->pg; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    a.d = c->d; a.pg = c->pg; a.site_g0 = site_g0(c);
     const int n = 2 * chains * (a.nkeep / 2);
     a.tau_min = n > 1 ? 1.0 / log10((double)n) : 0.0;
     a.in_lds = diag_lds_doubles(chains, a.nkeep, true) * 8 + 1024 <= LDS_CAP;
     const size_t lds = diag_lds_doubles(chains, a.nkeep, a.in_lds != 0) * 8;
-    if (set_lds(k_draw_diag, lds)) return -1;
     StreamSync sync{c->stream};
     if (upload_draws(c, src, &a.draws)) return -1;
     const size_t nout = (size_t)count * P * EPX_DG_COUNT;
     HIPCHK(c->diag_out.grow(nout));
     a.out = c->diag_out;
-    hipLaunchKernelGGL(k_draw_diag, dim3((unsigned)count, (unsigned)((P + EPX_DG_TILE - 1) / EPX_DG_TILE)), dim3(256), lds,
-                       c->stream, a);
-    HIPCHK(hipGetLastError());
+    const dim3 grid((unsigned)count, (unsigned)((P + EPX_DG_TILE - 1) / EPX_DG_TILE));
+    if (launch(k_draw_diag, grid, dim3(256), lds, c->stream, a)) return -1;
     HIPCHK(hipMemcpyAsync(out, a.out, nout * 8, hipMemcpyDeviceToHost, c->stream));
     if (nsamp) *nsamp = n;
     return sync.finish();
@@ -1845,7 +1747,7 @@ int epx_draw_rank_diagnostics(epx_ctx *c, int k0, int count, const double *theta
     if (chains > EPX_DG_MAX_CHAINS)
         return fail("epx_draw_rank_diagnostics: %d chains, at most %d", chains, (int)EPX_DG_MAX_CHAINS);
     a.k0 = k0; a.chains = chains; a.nkeep = S / chains; a.P = c->P;
-    a.d = c->d; a.pg = c->pg; a.site_g0 = c->multi ? (const int *)c->site_g0_d : nullptr;
+    a.d = c->d; a.pg = c->pg; a.site_g0 = site_g0(c);
     const long long n = 2ll * chains * (a.nkeep / 2);
     if (n > EPX_RD_MAX_DRAWS)
         return fail("epx_draw_rank_diagnostics: %lld used draws per site, at most %d (a coordinate's keys, draw indices and "
@@ -1854,14 +1756,12 @@ int epx_draw_rank_diagnostics(epx_ctx *c, int k0, int count, const double *theta
         return fail("epx_draw_rank_diagnostics: %d sites x %zu coordinates in one call, at most 2^31 - 1", count, P);
     a.tau_min = n > 1 ? 1.0 / log10((double)n) : 0.0;
     const size_t lds = rank_lds_bytes((int)n);
-    if (set_lds(k_rank_diag, lds)) return -1;
     StreamSync sync{c->stream};
     if (upload_draws(c, src, &a.draws)) return -1;
     const size_t nout = (size_t)count * P * EPX_RD_COUNT;
     HIPCHK(c->rank_out.grow(nout));
     a.out = c->rank_out;
-    hipLaunchKernelGGL(k_rank_diag, dim3((unsigned)((size_t)count * P)), dim3(EPX_RD_THREADS), lds, c->stream, a);
-    HIPCHK(hipGetLastError());
+    if (launch(k_rank_diag, dim3((unsigned)((size_t)count * P)), dim3(EPX_RD_THREADS), lds, c->stream, a)) return -1;
     HIPCHK(hipMemcpyAsync(out, a.out, nout * 8, hipMemcpyDeviceToHost, c->stream));
     if (nsamp) *nsamp = (int)n;
     return sync.finish();
@@ -1896,10 +1796,9 @@ int epx_pooled_moments(epx_ctx *c, int k0, int count, const double *center, cons
     double *center_d = a.out_sum + d;
     if (center) HIPCHK(hipMemcpyAsync(center_d, center, d * 8, hipMemcpyHostToDevice, c->stream));
     a.center = center ? center_d : nullptr;
-    hipLaunchKernelGGL(k_pooled_partial, dim3(pairs, a.nslab), dim3(256), 0, c->stream, a);
+    if (launch(k_pooled_partial, dim3(pairs, a.nslab), dim3(256), 0, c->stream, a)) return -1;
     const int nout = (int)((want_scatter ? d * d : 0) + d);
-    hipLaunchKernelGGL(k_pooled_final, dim3((nout + 255) / 256), dim3(256), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    if (launch(k_pooled_final, dim3((nout + 255) / 256), dim3(256), 0, c->stream, a)) return -1;
     HIPCHK(hipMemcpyAsync(sum, a.out_sum, d * 8, hipMemcpyDeviceToHost, c->stream));
     if (want_scatter) HIPCHK(hipMemcpyAsync(scatter, a.out_scatter, d * d * 8, hipMemcpyDeviceToHost, c->stream));
     *n = a.n;
@@ -2131,9 +2030,7 @@ int epx_psis_rows(int device, long long n, int S, const double *ll, double *out)
     HIPCHK(hipMemcpy(lld, ll, (size_t)n * S * 8, hipMemcpyHostToDevice));
     a.ll = lld; a.out = outd;
     const long long steps = (n + 15) / 16;
-    if (set_lds(k_psis_rows, lds)) return -1;
-    hipLaunchKernelGGL(k_psis_rows, dim3((unsigned)(steps < 65536 ? steps : 65536)), dim3(256), lds, 0, a);
-    HIPCHK(hipGetLastError());
+    if (launch(k_psis_rows, dim3((unsigned)(steps < 65536 ? steps : 65536)), dim3(256), lds, 0, a)) return -1;
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, outd, (size_t)n * 3 * 8, hipMemcpyDeviceToHost));
     return 0;
@@ -2157,9 +2054,7 @@ int epx_rank_normalize(int device, long long m, int n, const double *x, int fold
     HIPCHK(zd.alloc(total));
     HIPCHK(hipMemcpy(xd, x, total * 8, hipMemcpyHostToDevice));
     a.x = xd; a.rank = rd; a.z = zd;
-    if (set_lds(k_rank_normalize, lds)) return -1;
-    hipLaunchKernelGGL(k_rank_normalize, dim3((unsigned)m), dim3(EPX_RD_THREADS), lds, 0, a);
-    HIPCHK(hipGetLastError());
+    if (launch(k_rank_normalize, dim3((unsigned)m), dim3(EPX_RD_THREADS), lds, 0, a)) return -1;
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(rank_out, rd, total * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(z_out, zd, total * 8, hipMemcpyDeviceToHost));

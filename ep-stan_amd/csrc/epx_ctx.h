@@ -81,6 +81,25 @@ struct StreamSync {
 
 static const size_t LDS_CAP = epx::lds_capacity();
 
+// A kernel that asks for more dynamic LDS than the default 64 KiB has to be told so before its launch
+template <typename K>
+int set_lds(K kern, size_t bytes) {
+    if (bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return fail("hipFuncSetAttribute(%zu): %s", bytes, hipGetErrorString(e));
+    }
+    return 0;
+}
+
+// Queues a kernel that takes its argument struct by value, with `lds` bytes of dynamic LDS, and checks the launch
+template <typename Args>
+int launch(void (*kern)(Args), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args &a) {
+    if (set_lds(kern, lds)) return -1;
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 struct epx_ctx {
     int device = 0, model = 0, K = 0, D = 0, d = 0, P = 0;
     int64_t N = 0;
@@ -88,9 +107,10 @@ struct epx_ctx {
     std::vector<int64_t> k_lim;
     // multi-group sites (K < J): groups per site, device copies of the prefix sums / row limits
     std::vector<int> g_cnt;
+    std::vector<int> site_g0;       // K + 1: the first group of every site among all groups (one each without g_cnt)
     DevBuf<int> site_g0_d;
     DevBuf<int64_t> g_lim_d;
-    std::vector<int64_t> g_lim;     // host copy of the groups' row limits (epx_loo cuts its work items along them)
+    std::vector<int64_t> g_lim;     // host copy of the groups' row limits (epx_draws.h: cut_ctx_rows cuts work items along them)
     int multi = 0, ng_max = 0, nt_max = 0, pg = 0;
     int n_max = 0;
     // device buffers

@@ -428,7 +428,8 @@ int epx_newgroup_latents(int device, int model, int D, uint64_t seed, int32_t la
  * of the range), S is ignored; otherwise TEST HOOK: injected draws (count, S, P) row-major as epx_named_moments takes
  * them (a site reads its own coordinates of a record only).  nsamp out (may be NULL): draws per site.  At most D = 128
  * columns.  A tile's 16 x S log-likelihoods are kept in LDS while they fit (about 900 draws at D = 32; the environment variable
- * EPX_LOO_LDS_BYTES lowers the budget, for A/B runs and tests); longer runs keep them in a workspace sized by the grid:
+ * EPX_LOO_LDS_BYTES, read at every call, lowers the budget, for A/B runs and tests; a value that is no whole non-negative
+ * number is ignored, as for EPX_PO_LDS_BYTES); longer runs keep them in a workspace sized by the grid:
  * the same bits.  The tail, its candidates and the fit need about 16 (2.5 M + 106) doubles of LDS: an S beyond that (about 20000) is an error.  No
  * floating-point atomics: the same bits on every call.  Stream-ordered, one launch, one synchronisation. */
 enum epx_loo { EPX_LO_LPD = 0, EPX_LO_LL_MEAN, EPX_LO_LL_M2, EPX_LO_ELPD, EPX_LO_KHAT, EPX_LO_WESS, EPX_LO_COUNT };

@@ -2,8 +2,9 @@
 """Every array the entries over draws return, saved for a bit-for-bit comparison of two builds of libepx.so on one device:
 HipEngine.named_moments, named_order_stats, pooled_count_pass, predict, loo, draw_diagnostics and pooled_moments at the
 shapes of their tests/test_gpu_*.py files -- injected draws of single-group and multi-group models, and the sampler's own
-draws of a short run (whole range and a sub-range) -- with fixed seeds; and predict, loo, predict_new_group and
-newgroup_latents at the edges of the predictive kernels' row-tile walk (tile_edges).
+draws of a short run (whole range and a sub-range) -- with fixed seeds; predict, loo, predict_new_group and
+newgroup_latents at the edges of the predictive kernels' row-tile walk (tile_edges); and, at those edges and on the
+multi-group engines, replicated_checks, site_evidence, predict_order_stats and draw_rank_diagnostics (later_entries).
 
     python scripts/draw_entries_dump.py --out a.npz                      # this tree's library
     EPX_LIB=/path/to/other/libepx.so python scripts/draw_entries_dump.py --out b.npz
@@ -67,6 +68,35 @@ def entries(eng, tag, out, theta=None, chains=None, k0=0, count=None, seed=0):
     out[tag + '/pooled_sum_only'] = eng.pooled_moments(want_scatter=False, **kw)[1]
 
 
+def later_entries(eng, tag, out, theta, new_rows, seed=0):
+    """The entries over draws that came after those of `entries`, on all sites with injected draws of 4 chains:
+    replicated_checks with the per-draw sums, site_evidence with its terms (120 draws of its own: the fit set needs 2 P),
+    predict_order_stats of f and, Gaussian family, of the replicates (new_rows: new rows per site), draw_rank_diagnostics."""
+    from epstan_amd.engine import is_gauss
+    rng = np.random.RandomState(2000 + seed)
+    S = theta.shape[1]
+    groups, sites, draws = eng.replicated_checks(seed=5, row0=7, theta=theta, with_draws=True)
+    out[tag + '/ppc_groups'], out[tag + '/ppc_sites'], out[tag + '/ppc_draws'] = groups, sites, draws
+    if eng.D <= 32:                                      # (the proposal's factor of more coordinates does not fit the LDS)
+        for k in range(eng.K):
+            assert eng.cavity_site(k, 5.0 * np.eye(eng.d), np.zeros(eng.d), np.eye(eng.d), np.zeros(eng.d))
+        records, terms, _ = eng.site_evidence(seed=3, site0=2, theta=0.5 * rng.randn(eng.K, 120, eng.P) + 0.3, chains=4,
+                                              with_terms=True)
+        out[tag + '/evidence'] = records
+        for b, site in enumerate(terms):
+            for key, value in site.items():
+                out['%s/evidence_terms/%d/%s' % (tag, b, key)] = np.asarray(value)
+    row_lim = np.concatenate(([0], np.cumsum(new_rows)))
+    Xn = rng.randn(int(row_lim[-1]), eng.D)
+    group = None if eng.g_cnt is None else np.concatenate(
+        [rng.randint(0, int(eng.g_cnt[k]), n) for k, n in enumerate(new_rows)]).astype(np.int32)
+    ranks = np.unique([0, S // 4, S // 2, S - 1])
+    for what in ('f', 'yrep') if is_gauss(eng.model) else ('f',):
+        out['%s/predict_order_%s' % (tag, what)] = eng.predict_order_stats(Xn, row_lim, ranks, group, what=what, seed=13,
+                                                                           theta=theta)
+    out[tag + '/rank_diag'] = eng.draw_rank_diagnostics(theta=theta, chains=4)
+
+
 def tile_edges(out):
     """The predictive entries at the edges of their row-tile walk (csrc/predict_tile.h): an empty site, a full tile of 16
     rows, one row past a tile, one past a workgroup's 64; both homes of the LOO tile; a new group's pool of several
@@ -98,6 +128,7 @@ def tile_edges(out):
                 out['%s/newgroup%s-R%d-glpd' % (tag, name, R)] = glpd
                 out['%s/newgroup%s-R%d-N' % (tag, name, R)] = np.array(N)
         out[tag + '/latents'] = eng.newgroup_latents(9, 11, 3, 17, 3)
+        later_entries(eng, tag, out, theta, [3, 0, 16, 17, 65], seed=D)
         eng.close()
     for model in ('m4b_sg', 'm4a_sg'):
         X, y, k_lim = problem(model, 3, [7, 16, 17, 65], 78)
@@ -135,6 +166,8 @@ def dump(path):
         theta = 0.5 * np.random.RandomState(31).randn(3, 40, eng.P) + 0.3
         for k in range(3):                               # every site its own elements (the pool needs equal lengths)
             entries(eng, '%s-site%d' % (model, k), out, theta[k:k + 1], 4, k0=k, count=1, seed=k)
+        out[model + '/loo-sub'] = eng.loo(k0=1, count=2, theta=theta[1:3])      # (a sub-range starts at its own first group)
+        later_entries(eng, model + '-groups', out, theta, [3, 0, 17], seed=3)
         eng.close()
     # the sampler's own draws: a cavity of precision 4 I around 0 on every site, one short run
     K, D = 3, 3

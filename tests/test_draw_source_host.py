@@ -3,8 +3,13 @@ small host program that fills the plain fields of a context by hand and prints w
 
  * draw_source: where a call's draws come from, how many they are, and every refusal with the entry's name in it.
  * named_layout: the offsets of a row of named parameters against site_params.named_shape, for the context's largest
-   site (the per-site entries) and for every site's own group count (the pooled counting pass)."""
+   site (the per-site entries) and for every site's own group count (the pooled counting pass).
+ * cut_ctx_rows: the context's own rows cut into work items (epx_loo: items of 16 x tiles rows; epx_ppc and
+   epx_site_evidence: whole groups) and site_first, against the records written down here from the rows per group.
+ * check_rank_count, fill_ranks, pow2_pad: the rank list of the order-statistic entries and the padding of their keys.
+ * lds_budget: the one reader of EPX_PO_LDS_BYTES and EPX_LOO_LDS_BYTES."""
 
+import os
 import subprocess
 
 import numpy as np
@@ -71,3 +76,83 @@ def test_named_layout(probe, model, groups):
     for name in missing:
         out = subprocess.check_output(head + [str(sp.NAME_IDS['phi']), str(sp.NAME_IDS[name])]).decode().strip()
         assert out == 'refused named parameter %d is not defined by this site model' % sp.NAME_IDS[name]
+
+
+SINGLE = [[3], [0], [16], [17], [65]]                  # rows per group, site by site: one group everywhere (no g_cnt)
+MULTI = [[9], [8, 7, 9], [10, 6]]
+MULTI_EMPTY = [[9], [8, 0, 9], [10, 6]]                # (ctx_create refuses an empty group; the cutting does not depend on that)
+
+
+@pytest.mark.parametrize('item', [16, 64, 0])
+@pytest.mark.parametrize('sites', [SINGLE, MULTI, MULTI_EMPTY])
+def test_context_rows_cut_into_items(probe, sites, item):
+    K = len(sites)
+    g_cnt = [len(s) for s in sites]
+    g_lim = np.concatenate(([0], np.cumsum([n for s in sites for n in s])))
+    k_lim = np.concatenate(([0], np.cumsum([sum(s) for s in sites])))
+    for k0, count in ((0, K), (1, 2), (K - 1, 1)):
+        gi = sum(g_cnt[:k0])
+        want, first = [], [0]
+        for j in range(count):
+            for g in range(g_cnt[k0 + j]):
+                lo, hi = int(g_lim[gi]), int(g_lim[gi + 1])
+                gi += 1
+                if item == 0:                           # whole groups: one record each, an empty one too
+                    want.append((j, g, lo, hi - lo))
+                else:                                   # at most `item` rows: an empty group gives none
+                    want += [(j, g, r, min(item, hi - r)) for r in range(lo, hi, item)]
+            first.append(len(want))
+        rows = '/'.join(','.join(str(n) for n in s) for s in sites)
+        out = subprocess.check_output([probe, 'items', rows, str(k0), str(count), str(item)]).decode().splitlines()
+        got = [tuple(int(w) for w in line.split()[1:]) for line in out[:-1]]
+        assert all(line.startswith('wg ') for line in out[:-1]) and got == want, (sites, k0, count, item, got, want)
+        assert out[-1].split() == ['first'] + [str(f) for f in first], (sites, k0, count, item, out[-1])
+        # the records lie in the rows of their site, in order, and cover them
+        for j in range(count):
+            lo, hi = int(k_lim[k0 + j]), int(k_lim[k0 + j + 1])
+            mine = got[first[j]:first[j + 1]]
+            assert all(lo <= f and f + n <= hi and (item == 0 or 1 <= n <= item) for _, _, f, n in mine)
+            assert sum(n for _, _, _, n in mine) == hi - lo
+            assert [f for _, _, f, _ in mine] == sorted(f for _, _, f, _ in mine)
+        if item == 0:
+            assert len(got) == sum(g_cnt[k0:k0 + count])
+
+
+def _ranks(probe, who, S, ranks):
+    arg = 'null' if ranks is None else ','.join(str(r) for r in ranks) or 'none'
+    return subprocess.check_output([probe, 'ranks', who, str(S), arg]).decode().strip()
+
+
+@pytest.mark.parametrize('who', ['epx_named_order_stats', 'epx_predict_order_stats'])
+def test_rank_list(probe, who):
+    for S, ranks in ((5, [0]), (5, [0, 4]), (32, list(range(32)))):
+        assert _ranks(probe, who, S, ranks).split() == ['ok'] + [str(r) for r in ranks] + ['0'] * (32 - len(ranks))
+    for ranks in (None, [], list(range(33))):
+        n = 0 if ranks is None else len(ranks)
+        assert _ranks(probe, who, 64, ranks) == 'refused %s: between 1 and 32 ranks (got %d)' % (who, n)
+    assert _ranks(probe, who, 5, [5]) == 'refused %s: rank 5 outside [0, 5), the draws per site' % who
+    assert _ranks(probe, who, 5, [-1]) == 'refused %s: rank -1 outside [0, 5), the draws per site' % who
+    for ranks in ([2, 2], [3, 1]):
+        assert _ranks(probe, who, 5, ranks) == 'refused %s: the ranks have to be ascending and distinct' % who
+
+
+def test_power_of_two_padding(probe):
+    for S, want in ((1, '2 1'), (2, '2 1'), (3, '4 2'), (64, '64 6'), (65, '128 7')):
+        assert subprocess.check_output([probe, 'pad', str(S)]).decode().strip() == want
+
+
+@pytest.mark.parametrize('var', ['EPX_PO_LDS_BYTES', 'EPX_LOO_LDS_BYTES'])
+def test_lds_budget_knob(probe, var):
+    def budget(value):
+        env = {k: v for k, v in os.environ.items() if k != var}
+        if value is not None:
+            env[var] = value
+        return subprocess.check_output([probe, 'budget', var, '1000'], env=env).decode().rstrip('\n')
+
+    assert budget(None) == '1000|'
+    for value in ('0', '999'):                          # lowered: the note is what epx_predict_order_stats appends to a refusal
+        assert budget(value) == "%s|; %s = %s lowers the keys' budget" % (value, var, value)
+    for value in ('1000', '5000'):                      # nothing lowered, nothing said
+        assert budget(value) == '1000|'
+    for junk in ('', 'lots', '12k', '-1'):              # no whole non-negative number: ignored
+        assert budget(junk) == '1000|'

@@ -238,6 +238,9 @@ def test_multi_group_sites_read_their_own_coordinates(model):
         group = np.concatenate([np.full(n, g) for g, n in enumerate(groups[k])])
         _assert_loo_site(model, D, int(g_cnt[k]), theta[k, :, :eng.site_P[k]], X[sl], group, y[sl], got[sl], eng,
                          'site %d' % k)
+    # a sub-range starts at its own first group: the same bytes as those rows of the whole range
+    sub = eng.loo(k0=1, count=2, theta=theta[1:3])
+    assert sub.tobytes() == got[k_lim[1]:k_lim[3]].tobytes()
     eng.close()
 
 
