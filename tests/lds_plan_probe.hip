@@ -7,8 +7,9 @@
 // Shapes: (P, d) below, dp in {4, 8, 16, 32}, n_max in {1, 16, 48, 500, 2048, the largest whose plan still fits 160 KB},
 // max_depth in {1, 2, 3, 4, 10, 12}.
 //   L lines   every form x (P, d) x dp at the largest n_max, max_depth 10: each record size at each of its arguments
-//   M lines   every form x n_max x max_depth at the two shapes the device tests run, (P, d, dp) = (51, 34, 16), (99, 66, 32):
-//             where Omega, the tree stack, its lowest levels and the speculative kernel's records go in and out of LDS
+//   M lines   every form x n_max x max_depth at (P, d, dp) = (51, 34, 16), (99, 66, 32): where Omega, the tree stack, its
+//             lowest levels and the speculative kernel's records go in and out of LDS (the kernels these plans select
+//             are run, one row below and at every such boundary, from the table tests/resident_edge_cases.py)
 //   ALL line  count and FNV-1a hash of the lines of the WHOLE cross product form x (P, d) x dp x n_max x max_depth
 //   S lines   nuts_stream_lds_bytes: nv in {1, 2, 7}, resident (dpb 16, 32) and streaming (dpb 64, 128)
 // A line: tag form wpc cpb rw grp ngmax gauss | P d dp n_max max_depth | n_max off_y off_xch off_gl off_Om off_tail off_slot
